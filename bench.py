@@ -28,8 +28,18 @@ behind 600 ... 5000 ticks 8.0e8, `tools/window_probe.py`), so a
 training loop runs in.
 
 Prints ONE JSON line (rank 0).  `value` counts the full tick (update_env included: more work than the metric's
-literal "env.step + policy fwd", never less); `variant_policy_plus_step` is the literal variant (i) of BASELINE.md 3
-(get_action + step, update_env untimed), measured with HIP events.  `cpu_baseline` = oracle/cpu_bench.py.
+literal "env.step + policy fwd", never less); `ms_per_step` = the wall time of one timed step.
+
+A plain run does only what that headline needs: set-up (burn-in), warm-up, the K timed steps, the line.  `--full` adds every
+other figure, each measured after the timed region: the per-kernel roofline (HIP events; the launch's two halves from the tuning
+library), `variant_policy_plus_step` = the literal variant (i) of BASELINE.md 3 (get_action + step, update_env untimed), the
+`api_trainer`, `c5` and `single_world` legs and `cpu_baseline` = oracle/cpu_bench.py.  The `--no-*` options drop single legs of a
+--full run; in a plain run those keys are null.
+
+--dump-outputs DIR: after the timed region, what its last step left for a caller of the timed path -- the world state, actions,
+rewards, done flags, src maps, the two observation buffers (a fixed, seeded sample of their rows) and the region's counters --
+as DIR/<name>.npy in float32 / float64 (~20 MB).  The inputs are fixed by the arguments, so two builds can be compared output by
+output.
 """
 import argparse
 import json
@@ -164,6 +174,41 @@ class StreamGroups:
     def check_error_flag(self):
         for dw in self.parts:
             dw.check_error_flag()
+
+
+DUMP_MAX_WORLDS = 256    # worlds per process in a dump (more: a fixed, seeded sample of them) -- ~20 MB in all at slot_cap 256
+OBS_SAMPLE_ROWS = 8192   # observation rows per buffer in a dump (of worlds x slot_cap: 65,536 at 256 worlds, 40 MB each in full)
+
+
+def dump_outputs(parts, out_dir, suffix=""):
+    """--dump-outputs: what the timed path's last step left in the buffers a caller of DeviceWorlds.run / act + tick_refill reads --
+    every world-state array, actions, n_acted, rewards, done flags, src maps, the timed region's counters, and a fixed, seeded sample
+    of the rows of Agent.state / Agent.state_prime -- as out_dir/<name><suffix>.npy.  float32 arrays stay float32, everything else
+    is written as float64 (exact for every integer these arrays hold).  `parts`: the DeviceWorlds of this process, in world order."""
+    n_worlds = sum(dw.R for dw in parts)
+    worlds = np.arange(n_worlds)
+    if n_worlds > DUMP_MAX_WORLDS:
+        worlds = np.sort(np.random.RandomState(1).choice(n_worlds, DUMP_MAX_WORLDS, replace=False))
+
+    def cat(get):   # this process's worlds in order, the dumped ones selected on the device
+        t = torch.cat([get(dw) for dw in parts]) if len(parts) > 1 else get(parts[0])
+        return t[torch.as_tensor(worlds, device=t.device)].cpu().numpy()
+    arrays = {name: cat(lambda dw, n=name: dw.s[n]) for name in parts[0].s.keys()}
+    for name in ("actions", "n_acted", "reward", "done", "src1", "src2"):
+        arrays[name] = cat(lambda dw, n=name: getattr(dw, n))
+    arrays["acted_total"] = np.array([sum(int(dw.acted_total.item()) for dw in parts)])
+    arrays["refill_count"] = np.array([sum(int(dw.refill_count.item()) for dw in parts)])
+    if n_worlds > DUMP_MAX_WORLDS:
+        arrays["dump_worlds"] = worlds   # the worlds (this process's index) that the per-world arrays hold
+    obs = {"obs_state": cat(lambda dw: dw.obs_state()), "obs_state_prime": cat(lambda dw: dw.obs_state_prime())}
+    rows = obs["obs_state"].shape[0] * obs["obs_state"].shape[1]
+    pick = np.sort(np.random.RandomState(0).choice(rows, min(rows, OBS_SAMPLE_ROWS), replace=False))
+    arrays["obs_sample_rows"] = pick   # flat (dumped world * slot_cap + slot) index of every sampled row
+    for name, a in obs.items():
+        arrays[name + "_sample"] = a.reshape(rows, a.shape[-1])[pick]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
 
 
 def cpu_baseline(args):
@@ -517,7 +562,13 @@ def main():
                     help="process-group backend: nccl = RCCL over xGMI (the product); gloo = dry run of the N > 1 path (collectives hop through the host)")
     ap.add_argument("--share-gpu", action="store_true", help="dry run: every rank on cuda:0 (needs --dist-backend gloo)")
     ap.add_argument("--dist-timeout", type=float, default=180.0, help="process-group timeout in seconds (rendezvous and every collective)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline / kernel timing, api_trainer, c5, single_world, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs of its last step as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps and the headline line, nothing else
+        args.no_kernel_timing = args.no_cpu_baseline = args.no_api_trainer = args.no_c5 = args.no_single_world = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_torchrun(args)
@@ -603,6 +654,8 @@ def main():
     torch.cuda.synchronize()
     elapsed_bracket = time.perf_counter() - t0
     (grp or dw).check_error_flag()
+    if args.dump_outputs:   # (before any --full leg advances the worlds further)
+        dump_outputs(grp.parts if grp else [dw], args.dump_outputs, "_rank%d" % rank if world_size > 1 else "")
 
     # the only collective of the job: ONE RCCL all-gather of every rank's [agent-steps, refills, world_base, bracket, start, end, own elapsed]
     # row over xGMI (reinlife_amd/distributed.py); executed whenever a process group exists, also with one rank.  (Nanoseconds of

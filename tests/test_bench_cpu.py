@@ -65,3 +65,10 @@ def test_bench_exits_before_touching_a_device_when_the_job_does_not_fit():
     assert rc != 0 and "--gpus 2 but WORLD_SIZE=3" in msg and "Traceback" not in msg
     rc, msg = run({"WORLD_SIZE": "2", "RANK": "1", "LOCAL_RANK": "1"}, "--gpus", "2")
     assert rc != 0 and "LOCAL_RANK 1 but only 0 GPUs visible" in msg and "Traceback" not in msg
+
+
+def test_the_full_and_dump_options_exist():
+    """A plain line measures the headline alone; --full adds every other figure; --dump-outputs DIR writes the timed path's outputs."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "--full" in out.stdout and "--dump-outputs DIR" in out.stdout

@@ -301,7 +301,7 @@ def _bench(extra_env, *args):
     env = dict(os.environ, **extra_env)
     env.pop("RL_WORLD_BLOCK", None); env.pop("RL_WORLD_GENERIC", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--burnin", "40", "--worlds", "64",
-                          "--no-cpu-baseline", "--no-kernel-timing", *args], env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-kernel-timing", *args], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     return json.loads(out.stdout.strip().splitlines()[-1])
 
@@ -328,6 +328,58 @@ def test_bench_rccl_path_at_world_size_one_reduces_the_same_counters():
     for key in ("agent_steps", "mean_agents_per_world", "world_refills", "worlds_total"):
         assert plain["config"][key] == dist["config"][key], key
     assert plain["config"]["agent_steps"] > 30 * 64 * 60
+
+
+def test_plain_bench_line_times_its_steps_and_dumps_what_the_timed_path_computed(tmp_path):
+    """Without --full the line carries the headline alone, over exactly --steps timed steps.  --dump-outputs writes what the timed
+    region's last step left (float32 / float64, under 64 MB): the same in two runs with the same arguments, and the same as the
+    burn-in, warm-up and timed launches replayed here on a fresh handle."""
+    import argparse
+    import torch
+    import bench
+
+    def run(d):
+        env = dict(os.environ)
+        env.pop("RL_WORLD_BLOCK", None); env.pop("RL_WORLD_GENERIC", None)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--burnin", "40", "--worlds", "64",
+                              "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads(out.stdout.strip().splitlines()[-1])
+    da, db = tmp_path / "a", tmp_path / "b"
+    lines = [run(da), run(db)]
+    for line in lines:
+        assert line["steps"] == 30 and line["warmup"] == 5 and line["ms_per_step"] > 0
+        assert abs(line["value"] - line["config"]["agent_steps"] / (line["ms_per_step"] * 1e-3 * 30)) < 1e-3 * line["value"]
+        for key in ("roofline", "cpu_baseline", "api_trainer", "c5", "single_world"):
+            assert line[key] is None, key
+    names = sorted(os.listdir(da))
+    assert names == sorted(os.listdir(db))
+    assert {"actions.npy", "reward.npy", "done.npy", "cell_type.npy", "a_health.npy", "obs_state_sample.npy", "obs_state_prime_sample.npy"} <= set(names)
+    got, total = {}, 0
+    for n in names:
+        x, y = np.load(da / n), np.load(db / n)
+        assert x.dtype in (np.float32, np.float64), n
+        np.testing.assert_array_equal(x, y, err_msg=n)
+        got[n[:-4]] = x
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert got["acted_total"][0] == lines[0]["config"]["agent_steps"] == lines[1]["config"]["agent_steps"]
+    # the same launches on a fresh handle in this process
+    dw = bench.make_worlds(argparse.Namespace(worlds=64, workload="c4", seed=20260928), 0, "cuda:0")
+    for n in (40, 5):
+        bench.run_ticks(dw, n, True)
+    dw.acted_total.zero_(); dw.refill_count.zero_()
+    bench.run_ticks(dw, 30, True)
+    torch.cuda.synchronize()
+    dw.check_error_flag()
+    for key in dw.s:
+        np.testing.assert_array_equal(got[key], dw.s[key].cpu().numpy(), err_msg=key)
+    for key in ("actions", "n_acted", "reward", "done", "src1", "src2"):
+        np.testing.assert_array_equal(got[key], getattr(dw, key).cpu().numpy(), err_msg=key)
+    rows = got["obs_sample_rows"].astype(np.int64)
+    np.testing.assert_array_equal(got["obs_state_sample"], dw.obs_state().cpu().numpy().reshape(-1, 153)[rows])
+    np.testing.assert_array_equal(got["obs_state_prime_sample"], dw.obs_state_prime().cpu().numpy().reshape(-1, 153)[rows])
+    assert got["acted_total"][0] == int(dw.acted_total.item())
 
 
 def test_bench_refuses_more_gpus_than_there_are():

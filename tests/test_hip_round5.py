@@ -13,7 +13,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "30", "--warmup", "5", "--burnin", "40", "--no-cpu-baseline"]
+COMMON = ["--steps", "30", "--warmup", "5", "--burnin", "40", "--full", "--no-cpu-baseline"]
 
 
 def _bench(*args, timeout=900, drop=()):

@@ -5,6 +5,7 @@
 # `traffic`, `roofline_tick.traffic`, `roofline_policy.traffic` and `latency_bound_us` in them are this run's own.
 TAG=${1:-r6final}
 cd $GRAFT_REPO_ROOT
+ROOT=$PWD
 O=gpurun_out/$TAG; mkdir -p $O/w
 L=reinlife_amd/lib
 H=$(python -c "from reinlife_amd import build; print(build.source_hash())")
@@ -39,15 +40,15 @@ m = json.load(open("$O/latency_model.json")); m["inputs"] = {"ubench": "profiles
 json.dump(m, open("profiles/latency_model.json", "w"), indent=1); json.dump(m, open("$O/latency_model.json", "w"), indent=1)
 PY
 # ---- 5. the bench lines (traffic + latency model of THIS run in them), rocprofv3 kernel stats of the default command
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-timeout 300 python bench.py --steps 20 --warmup 5 > $O/bench_driver_window.json 2>> $O/bench.err
-timeout 300 python bench.py --path two-launch --no-cpu-baseline > $O/bench_two_launch.json 2>> $O/bench.err
-timeout 300 python bench.py --workload c5 --no-cpu-baseline > $O/bench_c5.json 2>> $O/bench.err
-timeout 900 python bench.py --gpus 2 --dist-backend gloo --share-gpu --worlds 128 --steps 20 --warmup 5 > $O/bench_2rank_dry.json 2>> $O/bench.err
-for w in 512 768 1024 2048 4096; do timeout 400 python bench.py --worlds $w --no-cpu-baseline --no-api-trainer --no-single-world > $O/w/bench_${w}worlds.json 2>/dev/null; done
-(cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$O/prof -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-kernel-timing --no-api-trainer --no-single-world > $GRAFT_REPO_ROOT/$O/prof.log 2>&1)
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_window.json 2>> $O/bench.err
+timeout 300 python bench.py --full --path two-launch --no-cpu-baseline > $O/bench_two_launch.json 2>> $O/bench.err
+timeout 300 python bench.py --full --workload c5 --no-cpu-baseline > $O/bench_c5.json 2>> $O/bench.err
+timeout 900 python bench.py --full --gpus 2 --dist-backend gloo --share-gpu --worlds 128 --steps 20 --warmup 5 > $O/bench_2rank_dry.json 2>> $O/bench.err
+for w in 512 768 1024 2048 4096; do timeout 400 python bench.py --full --worlds $w --no-cpu-baseline --no-api-trainer --no-single-world > $O/w/bench_${w}worlds.json 2>/dev/null; done
+(cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $ROOT/$O/prof -- python $ROOT/bench.py --full --no-cpu-baseline --no-kernel-timing --no-api-trainer --no-single-world > $ROOT/$O/prof.log 2>&1)
 DB=$(ls -t $O/prof/*/*_results.db 2>/dev/null | head -1)
-[ -n "$DB" ] && { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-kernel-timing --no-api-trainer --no-single-world  (r06, kernel sources $H)"
+[ -n "$DB" ] && { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-kernel-timing --no-api-trainer --no-single-world  (r06, kernel sources $H)"
   echo "# k_run<512, true, 2, 0> is launched three times: burn-in (2000 ticks), warm-up (300 ticks), TIMED REGION (2000 ticks): see the per-call line; k_run<512, true, 4, 0> = the c5 leg (1000 + 1000 ticks)"
   python tools/rocpd_summary.py $DB; } > $O/kernel_stats.txt; head -12 $O/kernel_stats.txt
 rm -rf $O/prof
