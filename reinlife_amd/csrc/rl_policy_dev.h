@@ -517,6 +517,8 @@ constexpr int kDenseTiles = 4;       // tiles (waves) per workgroup
 // ---------------------------------------------------------------------------------------------------------------
 // LDS block of one brain for policy_tile1s: [l1 | l2a | l2b][256] epilogue constants, then the heads' [unscale 8 | bias 8] (advantage, value)
 constexpr int kTileConstFloats = 3 * 256 + 2 * 16;
+// ... and in k_run, behind them, the value bound of the certified argmax (tile1_finish_cert): [K0, K1, -, -], |v| <= K0 + K1 * Z
+constexpr int kTileCertFloats = 4;
 
 // Weight ring over the 2 * NS steps of a layer taken as two passes: step i = K-chunk i % NS of output tiles 2 * (i / NS), +1.
 template <int NS, int D, int STEPS = 2 * NS, int TOUT = 4>   // STEPS = NS: one pass only (the caller offsets the base by its tile pair); TOUT: output tiles of the layer
@@ -747,10 +749,163 @@ struct Tile1Part {
     float head[4];
     rl_u4 draw;
 };
-template <int KIND, bool COHERENT, bool PAIR = false, int XM = 0>   // XM: what is known about the rows (in_chunk_class): 0 nothing, 1 RL_XF_SCALE, 2 + RL_XF_INT_HEALTH
+
+// ---------------------------------------------------------------------------------------------------------------
+// The certified argmax: where nothing but the action reads the dueling output (k_run, TRAIN 0 / 1: no Q values are
+// stored), the value V of a row shifts its eight q_i by the same amount, so it can change the action only through the f32 rounding of
+// q_i = fl(fl(a_i + v) - m) (tile1_finish: a_i = advantage + bias, m = (((a_0 + a_1) + ...) + a_7) * 0.125).  Proof that the action is
+// i* = the first argmax of a wherever the test below passes:
+//   1. Rounding to nearest is monotone, so a_j <= a_k gives q_j <= q_k: no j > i* is picked (the pick is the FIRST maximum of q), and
+//      the action is i* unless some j < i* (a_j < a_i*) rounds to q_j == q_i*.
+//   2. With B >= max(|a_i + v|, |fl(a_i + v) - m|) each of the two roundings moves a value by at most 2^-24 B, so a_i* - a_j > 2^-22 B
+//      already gives q_j < q_i* (the test asks for twice that).
+//   3. A = max |a_i|: |m| <= A (1 + 2^-21), so B <= (2A + |v|)(1 + 2^-20).  The test fl(a_i* - a_j) > 2^-20 fl(2A + Vbar) with Vbar >=
+//      |v| (the two roundings of the test cost less than 2^-21 relative) then gives a_i* - a_j > 2^-20 (2A + |v|)(1 - 2^-21) > 2^-21 B.
+//   4. Vbar = K0 + K1 Z, K0 = (|b_v| + C0)(1 + 2^-8), K1 = C1 (1 + 2^-8), both rounded up (run_cert_bounds, k_run's launch start), Z the
+//      row's largest input-layer activation (after the ReLU: >= 0; the value branch's input).  C0 = sum_k |w_k| |b1_k|, C1 = sum_k |w_k|
+//      sum_l |W1_kl| over the PACKED weights the value branch multiplies by (|hi| + |lo| times the feature's unscale, <= the f32 weight):
+//      the value branch computes v = fl(head + b_v), head = sum_k w_k y_k, y_k = relu(sum_l W1_kl z_l + b1_k), where every split of an
+//      operand row (22 bits against the row maximum) enlarges a magnitude by at most 2^-21, every f32 accumulation (<= 384 products per
+//      output, MFMA or not) by at most 384 * 2^-24 < 2^-15, and each epilogue FMA / addition by 2^-24: |v| <= (|b_v| + C0 + C1 Z)(1 + 2^-13).
+//      The f64 sums behind C0 and C1 are exact to 2^-44 (run_cert_bounds).  So |v| <= Vbar with room to spare (2^-8 against 2^-13).
+//   5. NaN / Inf: the test is written !(gap > thr) -> fallback, and thr carries (s - s) with s = sum of the a_i, a NaN as soon as any a_i
+//      is NaN or infinite; a NaN or Inf weight makes K0 / K1 NaN or Inf; Z is finite or +Inf (ReLU).  i* == 0 needs no test: every row whose
+//      q's are all NaN (m or v NaN) picks 0 as well, and a row that picks 0 from the full path's point of view has q_0 maximal.
+// A row that explores (u < eps) takes its action from the draw either way.  A tile with a valid greedy row that fails the test runs the
+// value branch after all (tile1_cert_fallback: out of line, so the hot tile's register allocation stays what it is) and finishes as
+// tile1_finish -- the same bits as the full path for EVERY row, certified or not.
+#ifndef RL_CERT_COUNT   /* tuning builds (rl_run.hip): counters of greedy rows, certified rows, fallback tiles */
+#define RL_CERT_COUNT(greedy_mask, cert_mask, fell_back) do { } while (0)
+#endif
+template <int KIND>
+__device__ __attribute__((noinline, cold)) void tile1_cert_fallback(TileIO io, const f32x4* ex, float un1, f32x4 adv4, rl_u4 draw)
+{
+    // role 1's value branch of policy_tile1s<PAIR> (same weights, epilogue constants, B operand from the exchange buffer -- untouched until
+    // the policy half's closing barrier -- and the same instructions in the same order), then the full finish
+    extern __shared__ __attribute__((aligned(16))) char rl_dyn_lds[];
+    constexpr int D = 3;
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), h = lane >> 5;
+    const Layout L = layout_of(KIND);
+    const float* const consts = (const float*)(rl_dyn_lds + io.c_lds_off) + 32 * h;
+    const float* const hconsts = (const float*)(rl_dyn_lds + io.c_lds_off) + 768;
+    WRingH<8, D> w;
+    w.start(io.packed + L.l2b, lane);
+    f32x4 B2[8][kPlanes];
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+#pragma unroll
+        for (int pl = 0; pl < kPlanes; ++pl) B2[c][pl] = ex[(c * kPlanes + pl) * 64 + lane];
+    f32x16 A[4];
+    EpiStream ep;
+    float mrow = 0.0f;
+    k_pass<8, 0>(w, B2, A[0], A[1], [&](int) {});
+    ep.c = consts + 512;
+    k_pass<8, 1>(w, B2, A[2], A[3], [&](int slot) {
+        if (slot == 0) ep.fetch(0, 0);
+        if (slot >= 2 && slot < 34) ep.step(0, slot - 2, A[0], A[1], un1, mrow);
+    });
+    WRing<1, 1, 1, D> wh;
+    wh.start(io.packed + L.hb, lane, 0);
+    ep.fetch(2, 0);
+#pragma unroll
+    for (int e = 0; e < 32; ++e) ep.step(2, e, A[2], A[3], un1, mrow);
+    mrow = fmaxf(mrow, __shfl_xor(mrow, 32));
+    float sc2, un2;
+    row_scale(mrow, sc2, un2);
+    auto araw = [&](int c, int e) { return A[c >> 1][8 * (c & 1) + e]; };
+    float val[4];
+    head_stream<D>(wh, *(const f32x4*)(hconsts + 16 + 4 * h), araw, sc2, un2, val);
+    const float adv[4] = {adv4.x, adv4.y, adv4.z, adv4.w};
+    tile1_finish<KIND>(io, lane, adv, val[0] + hconsts[16 + 8], draw, *(const f32x4*)(hconsts + 8 + 4 * h));
+}
+// Role 0's finish without V: vbar >= |v| of the lane's row (see above), ex / un1 what the fallback needs.
+template <int KIND>
+__device__ inline void tile1_finish_cert(const TileIO& io, int lane, const float (&adv)[4], const rl_u4& draw, const float* hconsts, float vbar,
+                                         const f32x4* ex, float un1)
+{
+    const int h = lane >> 5;
+    const f32x4 ba = *(const f32x4*)(hconsts + 8 + 4 * h);
+    const float a4[4] = {adv[0] + ba.x, adv[1] + ba.y, adv[2] + ba.z, adv[3] + ba.w};   // (tile1_finish's a_i)
+    float o4[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o4[r] = __shfl_xor(a4[r], 32);
+    int act = 0;
+    bool greedy = false, ok = true;
+    if (h == 0) {
+        const float a[8] = {a4[0], a4[1], a4[2], a4[3], o4[0], o4[1], o4[2], o4[3]};
+        float best = a[0], amax = fabsf(a[0]), s = a[0];
+        int is = 0;
+#pragma unroll
+        for (int i = 1; i < 8; ++i) {
+            const bool gt = a[i] > best;   // first maximum, as tile1_finish over q
+            is = gt ? i : is; best = gt ? a[i] : best;
+            amax = fmaxf(amax, fabsf(a[i])); s += a[i];
+        }
+        // (+ 2^-80: a floor far above what a flushed denormal can move, and far below any gap that matters)
+        const float thr = 0x1p-20f * (((amax + amax) + vbar) + 0x1p-80f) + (s - s);
+#pragma unroll
+        for (int j = 0; j < 7; ++j) ok = ok && (j >= is || best - a[j] > thr);
+        const bool explore = (float)rl_u24(draw.x) < io.eps;
+        act = explore ? (int)(draw.y >> 29) : is;
+        greedy = io.valid && io.actions && !explore;
+    }
+    const bool need = greedy && !ok;
+    RL_CERT_COUNT(__ballot(greedy), __ballot(greedy && ok), __any(need));
+    if (__builtin_expect(__any(need), 0)) {   // (wave-uniform)
+        tile1_cert_fallback<KIND>(io, ex, un1, f32x4{adv[0], adv[1], adv[2], adv[3]}, draw);
+        return;
+    }
+    if (h == 0 && io.valid && io.actions) {
+        io.actions[io.row] = (int8_t)act;
+        if (io.lds_actions_off >= 0) {
+            extern __shared__ __attribute__((aligned(16))) char rl_dyn_lds[];
+            ((signed char*)rl_dyn_lds)[io.lds_actions_off + io.lds_slot] = (signed char)act;
+        }
+    }
+}
+
+// The thread's share (thread tid of 512) of C0 and C1 (above) of a dueling brain's packed weights pk: feature o's fragment units of the
+// value branch's hidden layer (plane pl, k-half lane >> 5: one 16-byte unit per K-step), its unscale and bias, and its weight in the value
+// head.  Sums of |f16| in f64 are exact; the products of powers of two and 22-bit values nearly so.
+__device__ inline void cert_bound_part(gfloat* __restrict__ pk, int tid, double& c0, double& c1)
+{
+    const Layout L = layout_of(RL_PERD3QN);
+    const int t2 = tid >> 7, pl = (tid >> 6) & 1, lane = tid & 63, oo = lane & 31, o = 32 * t2 + oo;
+    const int h = (oo >> 2) & 1, r = (oo & 3) + 4 * (oo >> 3);   // o = 32 t2 + (r & 3) + 8 (r >> 2) + 4 h: epilogue / head k order
+    gf32x4* f = (gf32x4*)(pk + L.l2b) + (t2 * kPlanes + pl) * 64 + lane;
+    f32x4 u[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) u[s] = f[s * 4 * kPlanes * 64];
+    const float un_o = pk[L.l2b + frag_floats(8, 4) + (t2 * 2 + h) * 32 + r], b1 = pk[L.l2b + frag_floats(8, 4) + (t2 * 2 + h) * 32 + 16 + r];
+    typedef const _Float16 __attribute__((address_space(1))) gf16;
+    gf16* hw = (gf16*)(pk + L.hb);
+    const int hidx = (((o >> 5) * 2 + (r >> 3)) * kPlanes * 64 + 32 * h) * 8 + (r & 7);   // head row 0, k = o: [t][c][plane][lane][e]
+    const double w = (double)fabsf((float)hw[hidx]) + (double)fabsf((float)hw[hidx + 64 * 8]);
+    const double un_v = (double)pk[L.hb + head_consts_off(4)];
+    double sum = 0.0;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        const f16x8 v = __builtin_bit_cast(f16x8, u[s]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sum += (double)fabsf((float)v[e]);
+    }
+    const double wv = w * un_v;
+    c1 = wv * (sum * (double)un_o);
+    c0 = (pl == 0 && lane < 32) ? wv * (double)fabsf(b1) : 0.0;
+}
+// f64 -> f32 rounded toward +infinity (a NaN stays NaN)
+__device__ inline float f32_up(double d)
+{
+    float f = (float)d;
+    if ((double)f < d) f = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, f) + (f >= 0.0f ? 1u : -1u));
+    return f;
+}
+
+template <int KIND, bool COHERENT, bool PAIR = false, int XM = 0, bool CERT = false>   // XM: what is known about the rows (in_chunk_class): 0 nothing, 1 RL_XF_SCALE, 2 + RL_XF_INT_HEALTH
 __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, const PairLds* pair_lds = nullptr, Tile1Part* part = nullptr)
 {
     static_assert(KIND == RL_D3QN || KIND == RL_PERD3QN, "one-wave tile: dueling kinds");
+    static_assert(!CERT || PAIR, "the certified argmax: the pair tile");
     extern __shared__ __attribute__((aligned(16))) char rl_dyn_lds[];
     constexpr int D = 3;
     const int h = lane >> 5;
@@ -837,8 +992,9 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
     f32x4 B2[8][kPlanes];
     float sc1, un1;
     auto fraw = [&](int c, int e) { return F[c >> 1][8 * (c & 1) + e]; };
+    [[maybe_unused]] float zrow = 0.0f;   // CERT: the row's largest input-layer activation (the value branch's input)
     if (PAIR) {
-        w2.start(packed + l2, lane);
+        if (!(CERT && role)) w2.start(packed + l2, lane);   // (CERT: role 1 has no branch of its own)
         ep.c = consts + role * 128;   // tiles 2 * role, + 1
         ep.fetch(0, 0);
 #pragma unroll
@@ -847,6 +1003,7 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
         pair_lds->pmax[role * 64 + lane] = mrow;
         lds_barrier();
         mrow = fmaxf(mrow, pair_lds->pmax[(role ^ 1) * 64 + lane]);
+        zrow = mrow;
         row_scale(mrow, sc1, un1);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {   // own chunks: registers 8 (c & 1) .. of own tile c >> 1 = chunk 4 * role + c of the layer
@@ -857,6 +1014,7 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
             pair_lds->ex[((4 * role + c) * kPlanes + 1) * 64 + lane] = lo;
         }
         lds_barrier();
+        if (CERT && role) { RL_PMARK1(9); return; }   // V is not computed (tile1_finish_cert): role 1 is done with the input layer
 #pragma unroll
         for (int c = 0; c < 8; ++c)
 #pragma unroll
@@ -912,6 +1070,12 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
     RL_PMARK1(6);
     if (PAIR) {
         head_stream<D>(wh, *(const f32x4*)(hconsts + ((PAIR && role) ? 16 : 0) + 4 * h), araw, sc2, un2, adv);
+        if constexpr (CERT) {   // role 0 (role 1 left after the exchange): the action without V, or the value branch after all
+            const float* const kc = hconsts + kTileConstFloats - 768;
+            tile1_finish_cert<KIND>(io, lane, adv, draw, hconsts, __builtin_fmaf(kc[1], zrow, kc[0]), pair_lds->ex, un1);
+            RL_PMARK1(9);
+            return;
+        }
         if (role) { if (h == 0) pair_lds->val[lane] = adv[0] + hconsts[16 + 8]; }
         else {
 #pragma unroll

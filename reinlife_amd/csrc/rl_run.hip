@@ -17,12 +17,16 @@
 #ifndef RL_XM_ALL_DUELING_TILE   /* the dueling tile INSIDE the mixed-kind kernel (A/B: RL_XM_ALL_KERNEL, or 0 = one copy of it) */
 #define RL_XM_ALL_DUELING_TILE RL_XM_ALL_KERNEL
 #endif
+#ifndef RL_CERT_ALL   /* the certified argmax in the mixed-kind kernel too: A/B only (measured slower, run_policy_all) */
+#define RL_CERT_ALL 0
+#endif
 #ifndef RL_XM_ALL_KERNEL      /* 0: never; 2: tiles of worlds whose rows are known to be scaled by 2^10 with an integer health plane */
 #define RL_XM_ALL_KERNEL 2
 #endif
 
 // Measurement switch of the multi-tick launch (bench.py's per-half timings, tools/): 1 = skip the policy half, 2 = skip the tick half,
-// 4 / 8 / 16 = at most 2 / 1 / 3 policy tiles, 32 = no staggered start.  Results are then WRONG, so it exists in the TUNING builds only
+// 4 / 8 / 16 = at most 2 / 1 / 3 policy tiles, 32 = no staggered start, 64 = the full dueling finish (V computed) where the certified argmax
+// would run (same results, the A/B reference).  Results are then WRONG (but under 64 alone), so it exists in the TUNING builds only
 // (-DRL_TUNING: lib/libreinlife_hip_tune.so, and the stamped _prof build): the product library neither exports the switch nor compiles
 // the branches (RL_RUN_DBG is the constant 0 there).
 #ifdef RL_TUNING
@@ -32,8 +36,28 @@ extern "C" __attribute__((visibility("default"))) void rl_debug_set_run_mask(int
 extern "C" __attribute__((visibility("default"))) int rl_debug_get_run_mask(void) { return g_run_debug; }
 #endif
 #define RL_RUN_DBG(ka) (*(const int __attribute__((address_space(4)))*)&(ka)->ra.debug)
+// counters of the certified argmax (tile1_finish_cert): greedy rows, certified rows, fallback tiles -- per translation unit (unit 0: the
+// dueling-kind kernels, unit 1: kKindAll), read and cleared by rl_debug_cert_counters(_all)
+static __device__ unsigned long long g_cert_counts[4];
+#define RL_CERT_COUNT(greedy_mask, cert_mask, fell_back) do { \
+        const unsigned long long gm_ = (greedy_mask), cm_ = (cert_mask); const bool fb_ = (fell_back); \
+        if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0) { \
+            atomicAdd(&g_cert_counts[0], (unsigned long long)__popcll(gm_)); atomicAdd(&g_cert_counts[1], (unsigned long long)__popcll(cm_)); \
+            if (fb_) atomicAdd(&g_cert_counts[2], 1ull); } } while (0)
 #else
 #define RL_RUN_DBG(ka) 0
+#endif
+#ifdef RL_TUNING   /* out[0..2] = the counters of this unit's kernels since the last call (cleared) */
+#if defined(RL_RUN_UNIT) && RL_RUN_UNIT == 1
+extern "C" __attribute__((visibility("default"))) int rl_debug_cert_counters_all(unsigned long long* out)
+#else
+extern "C" __attribute__((visibility("default"))) int rl_debug_cert_counters(unsigned long long* out)
+#endif
+{
+    const unsigned long long zero[4] = {0, 0, 0, 0};
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(out, HIP_SYMBOL(g_cert_counts), sizeof(zero)) != hipSuccess) return -1;
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_cert_counts), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
+}
 #endif
 
 namespace {
@@ -115,7 +139,8 @@ constexpr int kMaxTiles = 32;                // 32-row tiles of one brain per wo
 constexpr int kPairFloats = 32 + 2 * 64;     // per tile pair: row values, partial row maxima of the two roles
 constexpr int kPairExBytes = 8 * kPlanes * 64 * 16;   // per tile pair: the split activations of the input layer (aliases the Agent.state mirror)
 constexpr int kPairFloatsAll = kPairValFloats + 2 * 64;   // kKindAll: role 1's head partials (4 per lane), then the partial row maxima
-template <int KIND> __host__ __device__ constexpr int run_const_floats() { return KIND == kKindAll ? kTileConstMax : kTileConstFloats; }
+template <int KIND> __host__ __device__ constexpr int run_const_floats() { return KIND == kKindAll ? kTileConstMax : kTileConstFloats + kTileCertFloats; }
+static_assert(kTileConstFloats + kTileCertFloats <= kTileConstMax, "kKindAll: the dueling block's value bound fits behind its constants");
 template <int KIND> __host__ __device__ constexpr int run_pair_floats() { return KIND == kKindAll ? kPairFloatsAll : kPairFloats; }
 template <int KIND>
 __host__ __device__ inline size_t carve_policy(PolSmem& ps, char* base, size_t o, int cap, size_t mirror_budget = 0, int n_cbrains = 0,
@@ -461,9 +486,12 @@ __device__ __forceinline__ void run_policy1(const KParams& p, Smem& s, PolSmem& 
         }
     } else
     if (T == 512 && ps.pairv != nullptr && ntiles <= 4 && (size_t)ps.xrows * kXStride * sizeof(float) >= 4 * (size_t)kPairExBytes) {
-        // TWO waves per tile, on the same SIMD (waves i and i + 4): policy_tile1s<PAIR>
+        // TWO waves per tile, on the same SIMD (waves i and i + 4): policy_tile1s<PAIR>.  Where no Q value is stored (TRAIN 0 / 1) the
+        // tile certifies its argmax instead of computing V: role 1 leaves after the input layer, role 0 finishes inside
+        // the tile, and the barrier that carried V to role 0 goes away.  (Tuning builds: run mask 64 = the full path.)
         const int role = __builtin_amdgcn_readfirstlane(wave >> 2), slot = wave & 3;
         const bool have = slot < ntiles;
+        const bool cert = TRAIN != 2 && !(RL_RUN_DBG(ka) & 64);   // (uniform; a constant in the product)
         TileIO io;
         Tile1Part part;
         PairLds pl;
@@ -471,15 +499,18 @@ __device__ __forceinline__ void run_policy1(const KParams& p, Smem& s, PolSmem& 
         pl.ex = (f32x4*)((char*)ps.xmirror + (size_t)kPairExBytes * slot);
         if (have) {
             tile_io(slot, io, j);
-            policy_tile1s<KIND, RL_RUN_COHERENT, true, RL_XM_DUELING_KERNEL>(io, lane, role, &pl, &part);
+            if (cert) policy_tile1s<KIND, RL_RUN_COHERENT, true, RL_XM_DUELING_KERNEL, TRAIN != 2>(io, lane, role, &pl, &part);
+            else policy_tile1s<KIND, RL_RUN_COHERENT, true, RL_XM_DUELING_KERNEL>(io, lane, role, &pl, &part);
         } else { lds_barrier(); lds_barrier(); }   // (the two exchanges inside the tile)
 #ifdef RL_PHASE_PROFILE
         if (p.prof && (int)blockIdx.x == p.prof_world && lane == 0) p.prof[116 + wave] = (long long)clock64();   // (128 slots)
 #endif
-        lds_barrier();
-        if (have && role == 0) {   // (a fresh lane index: `lane` / `j` from above the tile lived through it -- spilled in the TRAIN instantiations, a reload behind vmcnt(0) right here)
-            const int fl = rl_lane_fresh();
-            tile1_finish<KIND>(io, fl, part.head, pl.val[fl & 31], part.draw, *(const f32x4*)((const float*)(smem_base + io.c_lds_off) + 768 + 8 + 4 * (fl >> 5)));
+        if (!cert) {
+            lds_barrier();
+            if (have && role == 0) {   // (a fresh lane index: `lane` / `j` from above the tile lived through it -- spilled in the TRAIN instantiations, a reload behind vmcnt(0) right here)
+                const int fl = rl_lane_fresh();
+                tile1_finish<KIND>(io, fl, part.head, pl.val[fl & 31], part.draw, *(const f32x4*)((const float*)(smem_base + io.c_lds_off) + 768 + 8 + 4 * (fl >> 5)));
+            }
         }
     } else
     for (int ti = wave; ti < ntiles; ti += T / 64) {
@@ -513,13 +544,14 @@ __device__ __forceinline__ void run_policy1(const KParams& p, Smem& s, PolSmem& 
 #else
 #define RL_XM_EXPECT(x) (x)
 #endif
+template <bool CERT>
 __device__ __attribute__((noinline, cold)) Tile1Part run_tile_general(TileIO io, PairLds pl, int role, int kind)
 {
     Tile1Part part;
     const int lane = rl_lane_fresh();
     if (kind == RL_DQN) policy_pair2<RL_DQN, RL_RUN_COHERENT>(io, lane, role, &pl, &part);
     else if (kind == RL_PPO) policy_pair2<RL_PPO, RL_RUN_COHERENT>(io, lane, role, &pl, &part);
-    else policy_tile1s<RL_PERD3QN, RL_RUN_COHERENT, true>(io, lane, role, &pl, &part);
+    else policy_tile1s<RL_PERD3QN, RL_RUN_COHERENT, true, 0, CERT>(io, lane, role, &pl, &part);
     return part;
 }
 
@@ -565,6 +597,14 @@ __device__ __forceinline__ void run_policy_all(const KParams& p, Smem& s, PolSme
         return task >= 0 ? ((task >> 20) & 7) : ((cint*)ka->ra.kind)[b];
     };
     // One tile on a pair of waves: policy_tile1s<PAIR> (dueling kinds) / policy_pair2 (DQN, PPO); every wave meets the same barriers.
+    // The certified argmax is NOT taken here: measured, configs[4] went from 25.8 to 26.4 us per tick with it (a dueling
+    // tile's roles share their SIMDs with DQN / PPO roles, whose MFMA streams fill what the value branch leaves; the finish inside the tile
+    // lengthens role 0 instead).  RL_CERT_ALL = 1 builds it for an A/B.
+    const bool cert = RL_CERT_ALL && TRAIN != 2 && !(RL_RUN_DBG(ka) & 64);   // (uniform; a constant in the product.  Tuning builds: run mask 64 = the full path)
+    auto duel = [&](auto xm, TileIO& io, int role, PairLds& pl, Tile1Part& part) {
+        if (cert) policy_tile1s<RL_PERD3QN, RL_RUN_COHERENT, true, decltype(xm)::value, TRAIN != 2>(io, lane, role, &pl, &part);
+        else policy_tile1s<RL_PERD3QN, RL_RUN_COHERENT, true, decltype(xm)::value>(io, lane, role, &pl, &part);
+    };
     auto pair_round = [&](bool have, int ti, int role, int slot, int ex_off, bool from_mirror, int task) {
         TileIO io;
         Tile1Part part;
@@ -577,16 +617,16 @@ __device__ __forceinline__ void run_policy_all(const KParams& p, Smem& s, PolSme
             // two copies of every tile: the rows of THIS world and tick are known to be scaled by 2^10 with exactly-zero lo halves in the
             // plane chunks (oflags[0], run_obs_flags: ~9 in 10 ticks) -- or nothing is assumed.  Bit-identical either way.
             const bool plain = kind == RL_DQN || kind == RL_PPO;
-            if (!plain && RL_XM_ALL_DUELING_TILE == 0) policy_tile1s<RL_PERD3QN, RL_RUN_COHERENT, true>(io, lane, role, &pl, &part);   // (ONE copy of this tile)
+            if (!plain && RL_XM_ALL_DUELING_TILE == 0) duel(IntC<0>{}, io, role, pl, part);   // (ONE copy of this tile)
             else if (RL_XM_EXPECT(rows_known)) {
                 if (kind == RL_DQN) policy_pair2<RL_DQN, RL_RUN_COHERENT, RL_XM_ALL_KERNEL>(io, lane, role, &pl, &part);
                 else if (kind == RL_PPO) policy_pair2<RL_PPO, RL_RUN_COHERENT, RL_XM_ALL_KERNEL>(io, lane, role, &pl, &part);
-                else policy_tile1s<RL_PERD3QN, RL_RUN_COHERENT, true, RL_XM_ALL_DUELING_TILE>(io, lane, role, &pl, &part);
-            } else if (RL_XM_COLD_CALL) part = run_tile_general(io, pl, role, kind);
+                else duel(IntC<RL_XM_ALL_DUELING_TILE>{}, io, role, pl, part);
+            } else if (RL_XM_COLD_CALL) part = cert ? run_tile_general<TRAIN != 2>(io, pl, role, kind) : run_tile_general<false>(io, pl, role, kind);
             else {
                 if (kind == RL_DQN) policy_pair2<RL_DQN, RL_RUN_COHERENT>(io, lane, role, &pl, &part);
                 else if (kind == RL_PPO) policy_pair2<RL_PPO, RL_RUN_COHERENT>(io, lane, role, &pl, &part);
-                else policy_tile1s<RL_PERD3QN, RL_RUN_COHERENT, true>(io, lane, role, &pl, &part);
+                else duel(IntC<0>{}, io, role, pl, part);
             }
         } else { lds_barrier(); lds_barrier(); }   // (the two exchanges inside a tile)
         lds_barrier();
@@ -594,7 +634,7 @@ __device__ __forceinline__ void run_policy_all(const KParams& p, Smem& s, PolSme
             const int fl = rl_lane_fresh();   // (not the lane index from above the tile: see run_policy1)
             if (kind == RL_DQN) pair_finish<RL_DQN>(io, fl, part, &pl);
             else if (kind == RL_PPO) pair_finish<RL_PPO>(io, fl, part, &pl);
-            else tile1_finish<RL_PERD3QN>(io, fl, part.head, pl.val[fl & 31], part.draw, *(const f32x4*)((const float*)(smem_base + io.c_lds_off) + 768 + 8 + 4 * (fl >> 5)));
+            else if (!cert) tile1_finish<RL_PERD3QN>(io, fl, part.head, pl.val[fl & 31], part.draw, *(const f32x4*)((const float*)(smem_base + io.c_lds_off) + 768 + 8 + 4 * (fl >> 5)));
         }
     };
     // meta[5] == 0: every tile in ONE round, the waves dealt over the SIMDs by cost (policy_schedule_wave0), rows from the mirror.
@@ -945,6 +985,46 @@ __device__ __forceinline__ void run_tick_call_fixed(RunParamsC* ka) { run_tick_b
 template <int T, int KIND, int TRAIN>
 __device__ __forceinline__ void run_tick_call_generic(RunParamsC* ka) { run_tick_body<T, false, KIND, TRAIN>(ka); }
 
+// The value bounds of the certified argmax (tile1_finish_cert) of every dueling brain, behind its LDS constants: K0 =
+// (|b_v| + C0)(1 + 2^-8) and K1 = C1 (1 + 2^-8), rounded up.  Each of the 512 threads takes its share of two brains at a time
+// (cert_bound_part: 8 x 16 bytes of each brain's value hidden layer), the waves' f64 sums cross through the policy's pair buffers (not in
+// use before the first tick), and after one barrier thread b writes brain b's pair.  The caller's barrier publishes them.
+template <int KIND>
+__device__ inline void run_cert_bounds(const KParams& p, PolSmem& ps, RunParamsC* ka, int tid)
+{
+    typedef const int __attribute__((address_space(4))) cint;
+    constexpr int CF = run_const_floats<KIND>();
+    const int nb = p.n_brains, wave = tid >> 6;
+    auto dueling = [&](int b) { return KIND != kKindAll || ((cint*)ka->ra.kind)[b] == RL_D3QN || ((cint*)ka->ra.kind)[b] == RL_PERD3QN; };
+    double* part = (double*)ps.pairv;   // [brain][wave][C0, C1]
+    for (int b0 = 0; b0 < nb; b0 += 2) {
+        double c[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int b = b0 + i;
+            c[i][0] = 0.0; c[i][1] = 0.0;
+            if (b < nb && dueling(b)) cert_bound_part((gfloat*)((const float* const __attribute__((address_space(4)))*)ka->ra.packed)[b], tid, c[i][0], c[i][1]);
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) { c[i][0] += __shfl_xor(c[i][0], off); c[i][1] += __shfl_xor(c[i][1], off); }
+        if ((tid & 63) == 0) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+                if (b0 + i < nb) { part[((b0 + i) * 8 + wave) * 2] = c[i][0]; part[((b0 + i) * 8 + wave) * 2 + 1] = c[i][1]; }
+        }
+    }
+    lds_barrier();
+    if (tid < nb && dueling(tid)) {
+        double c0 = 0.0, c1 = 0.0;
+        for (int w = 0; w < 8; ++w) { c0 += part[(tid * 8 + w) * 2]; c1 += part[(tid * 8 + w) * 2 + 1]; }
+        float* const k = ps.cconst + CF * tid;
+        k[kTileConstFloats] = f32_up(((double)fabsf(k[768 + 16 + 8]) + c0) * (1.0 + 0x1p-8));
+        k[kTileConstFloats + 1] = f32_up(c1 * (1.0 + 0x1p-8));
+    }
+}
+
 template <int T, bool FIXED, int KIND, int TRAIN>
 __device__ __forceinline__ void run_load_call(RunParamsC* ka)   // (inlined: load_world reads the kernel-argument segment through the intrinsic)
 {
@@ -988,7 +1068,7 @@ __device__ __forceinline__ void run_load_call(RunParamsC* ka)   // (inlined: loa
             const int kind = ((const int __attribute__((address_space(4)))*)ka->ra.kind)[b];
             return pk + tile_const_src(kind, min(j, tile_const_floats(kind) - 1));
         } else
-            return pk + tile_const_src(KIND, j);
+            return pk + tile_const_src(KIND, min(j, kTileConstFloats - 1));   // (the value bound behind them: run_cert_bounds)
     };
     if (ctotal > 0) {
 #pragma unroll
@@ -1057,6 +1137,7 @@ __device__ __forceinline__ void run_load_call(RunParamsC* ka)   // (inlined: loa
 #pragma unroll
             for (int u = 0; u < UC; ++u) { const int i = base + u * T + tid; if (i < ctotal) ps.cconst[i] = cv[u]; }
         }
+        if constexpr (T == 512 && (KIND != kKindAll || RL_CERT_ALL)) run_cert_bounds<KIND>(p, ps, ka, tid);   // (the pair tiles' certified argmax)
     }
     RL_MARK(94);
     lds_barrier();
