@@ -10,7 +10,8 @@
  *   rl_reset_synthetic Environment.reset()-style world generator  World/environment.py:133-158, 741-761
  *   rl_reset_families  Environment.reset() itself (one agent per brain) World/environment.py:133-158
  *   rl_policy_act      Agent.get_action() over all agents         World/entities.py:215-222 ->
- *                      DQN.py:126-139, D3QN.py:161-173, PERD3QN.py:198-210, PPO.py:101-106,164-169
+ *                      DQN.py:126-139, D3QN.py:161-173, PERD3QN.py:198-210, PPO.py:101-106,164-169,
+ *                      PERDQN.py:101-111,311-323
  *   rl_policy_forward  the bare network forward of one brain on a dense batch of observation rows
  *
  * Conventions
@@ -55,7 +56,7 @@ enum { RL_EMPTY = 0, RL_FOOD = 1, RL_POISON = 2, RL_AGENT = 3, RL_KIN = 4, RL_SU
 enum { RL_F_DEAD = 1, RL_F_REPRODUCED = 2, RL_F_KILLED = 4, RL_F_ATE_SUPER = 8, RL_F_INTER_KILLED = 16,
        RL_F_INTRA_KILLED = 32 };
 /* brain kinds (BasicBrain.method, Models/utils.py:1-14) */
-enum { RL_DQN = 0, RL_D3QN = 1, RL_PERD3QN = 2, RL_PPO = 3 };
+enum { RL_DQN = 0, RL_D3QN = 1, RL_PERD3QN = 2, RL_PPO = 3, RL_PERDQN = 4 };
 /* Philox draw sites */
 enum { RL_SITE_FOOD = 1, RL_SITE_REPRO = 2, RL_SITE_BIRTH = 3, RL_SITE_PRODUCE = 4, RL_SITE_ACT = 5,
        RL_SITE_RESET_AGENT = 6, RL_SITE_RESET_FOOD = 7, RL_SITE_RESET_POISON = 8, RL_SITE_RESET_SUPER = 9 };
@@ -151,7 +152,7 @@ typedef struct {
 
 /* One brain of the brains list. */
 typedef struct {
-    int32_t kind;            /* RL_DQN .. RL_PPO */
+    int32_t kind;            /* RL_DQN .. RL_PERDQN */
     float epsilon;           /* exploration rate (0 = greedy, training=False); ignored for PPO (always samples) */
     const float* packed;     /* device: weights in the layout produced by rl_policy_pack_weights */
 } rl_brain;
@@ -212,6 +213,8 @@ int rl_tick_refill(rl_world* h, const int8_t* actions, const rl_step_out* sout, 
  * workgroups per CU then take turns; the two-launch loop is faster there, which is why it is not the default).
  * Not in this library: the 256- and 1024-thread instantiations ("world_block" = 256 / 1024, dueling kinds only) exist in the tuning
  * build alone (libreinlife_hip_tune.so, RL_TUNE=1 python reinlife_amd/build.py); here they answer 0 / RL_E_UNSUPPORTED.
+ * A brains list that holds a PERDQN brain is not run here (k_run has no PERDQN tile): rl_run_supported() answers 0 and rl_run / rl_run_ex
+ * return RL_E_UNSUPPORTED, both naming PERDQN and the two-launch loop.
  * Otherwise RL_E_UNSUPPORTED: loop over rl_policy_act + rl_tick_refill. */
 /* rl_run_ex: rl_run with the options a TRAINING loop needs (Helpers/trainer.py:85-99 with training=True):
  *   eps_schedule  device [n_ticks][n_brains] or NULL: the brains' exploration rate in every tick of the launch -- the reference's brains
@@ -259,7 +262,7 @@ int64_t rl_policy_n_params(int kind);
 int64_t rl_policy_packed_floats(int kind);
 /* host -> host: state-dict order  (DQN: fc1.w fc1.b fc2.w fc2.b fc3.w fc3.b;  D3QN/PERD3QN: fc.w fc.b adv_fc1.w
  * adv_fc1.b adv_fc2.w adv_fc2.b value_fc1.w value_fc1.b value_fc2.w value_fc2.b;  PPO: fc1.w fc1.b fc2.w fc2.b
- * fc_pi.w fc_pi.b fc_v.w fc_v.b)  ->  MFMA-fragment-major layout read by the kernels */
+ * fc_pi.w fc_pi.b fc_v.w fc_v.b;  PERDQN: fc.0.w fc.0.b fc.2.w fc.2.b fc.4.w fc.4.b)  ->  MFMA-fragment-major layout read by the kernels */
 int rl_policy_pack_weights(int kind, const float* state_dict_flat, float* packed);
 /* dense batch: obs [n_rows][153] (device) -> out [n_rows][8]: Q values (per-row dueling mean) or PPO probabilities */
 int rl_policy_forward(int kind, const float* packed, const float* obs, int64_t n_rows, float* out, void* stream);

@@ -22,7 +22,7 @@ class SavedAgent:
         self.gene, self.brain = gene, brain
 
     def save_brain(self, path):  # entities.py:224-242
-        net = {"DQN": "agent", "D3QN": "eval_net", "PERD3QN": "eval_net", "PPO": "model"}[self.brain.method]
+        net = {"DQN": "agent", "D3QN": "eval_net", "PERD3QN": "eval_net", "PPO": "model", "PERDQN": "model"}[self.brain.method]
         torch.save(getattr(self.brain, net).state_dict(), path + ".pt")
 
 

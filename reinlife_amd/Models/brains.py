@@ -1,5 +1,5 @@
-"""The four brains of the hot path with the reference's constructor keywords, attribute names and state-dict keys
-(ReinLife/Models/DQN.py:18-63, D3QN.py:16-80, PERD3QN.py:10-79, PPO.py:10-52), so `load_model=` accepts the
+"""The five brains of the hot path with the reference's constructor keywords, attribute names and state-dict keys
+(ReinLife/Models/DQN.py:18-63, D3QN.py:16-80, PERD3QN.py:10-79, PPO.py:10-52, PERDQN.py:49-89), so `load_model=` accepts the
 reference's `pretrained/*.pt` files.  The forward pass and action selection run in libreinlife_hip.so (f32-grade block-scaled f16 MFMA):
 batched over all agents through Environment.act(), or one state at a time through get_action().
 
@@ -42,6 +42,12 @@ class _PPONet(nn.Module):  # PPO.py:95-98
         self.fc2 = nn.Linear(256, 256)
         self.fc_pi = nn.Linear(256, output_dim)
         self.fc_v = nn.Linear(256, 1)
+
+
+class _PERDQNNet(nn.Module):  # PERDQN.py:311-323
+    def __init__(self, state_size, action_size):
+        super().__init__()
+        self.fc = nn.Sequential(nn.Linear(state_size, 64), nn.ReLU(), nn.Linear(64, 64), nn.ReLU(), nn.Linear(64, action_size))
 
 
 _warned = [False]
@@ -245,3 +251,44 @@ class PPOAgent(_HipBrain):
         prob = (self.forward_batch(np.asarray(s)[None])[0] if out is None else out).cpu()
         a = int(torch.distributions.Categorical(prob).sample().item())  # PPO.py:164-169
         return a if self.load_model else (a, prob)
+
+
+class PERDQNAgent(_HipBrain):
+    kind = _lib.PERDQN
+
+    def __init__(self, input_dim=153, output_dim=8, explore_step=5_000, train_freq=20, learning_rate=0.001, batch_size=64,
+                 gamma=0.99, capacity=20000, load_model=False, training=True):
+        super().__init__(input_dim, output_dim, "PERDQN")
+        self.state_size, self.action_size = input_dim, output_dim
+        self.discount_factor, self.learning_rate, self.memory_size = gamma, learning_rate, capacity
+        self.epsilon, self.epsilon_min, self.explore_step = 1.0, 0.01, explore_step
+        self.epsilon_decay = (self.epsilon - self.epsilon_min) / self.explore_step
+        self.batch_size, self.train_start, self.train_freq = batch_size, 1000, train_freq
+        # torch's generator in the reference's order (PERDQN.py:74-76): model, xavier_uniform of its Linear weights, target model
+        self.model = _PERDQNNet(input_dim, output_dim)
+        for m in self.model.fc:
+            if isinstance(m, nn.Linear):
+                nn.init.xavier_uniform_(m.weight)
+        self.target_model = _PERDQNNet(input_dim, output_dim)
+        self.target_model.load_state_dict(self.model.state_dict())
+        self.training = training
+        if not self.training:
+            self.epsilon = 0
+        if load_model:
+            self.model.load_state_dict(torch.load(load_model))
+            self.model.eval()
+
+    def _net(self):
+        return self.model
+
+    def update_epsilon(self, n_epi):   # epsilon decays in train_model() alone (PERDQN.py:139-140), which learn() would reach
+        pass
+
+    def epsilon_schedule(self, n_epi, k):
+        return np.full(k, self.epsilon, np.float64)
+
+    def get_action(self, state, out=None):   # PERDQN.py:101-111: the np.random coin first, then random.randrange or the first argmax
+        if np.random.rand() <= self.epsilon:
+            return random.randrange(self.action_size)
+        q = self.forward_batch(np.asarray(state)[None])[0] if out is None else out
+        return int(q.argmax().item())

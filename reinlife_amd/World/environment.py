@@ -132,6 +132,8 @@ class AgentView:
         if b.method == "PPO":
             r = b.get_action(state, out=out)
             self.action, self.prob = r if isinstance(r, tuple) else (r, None)
+        elif b.method == "PERDQN":   # (its get_action takes no n_epi: entities.py:219-220)
+            self.action = b.get_action(state, out=out)
         else:
             self.action = b.get_action(state, n_epi, out=out)
 

@@ -12,8 +12,8 @@ N_BEST = 10
 FOOD_TRIES = 7
 EMPTY, FOOD, POISON, AGENT, KIN, SUPER_FOOD = 0, 1, 2, 3, 4, 5
 F_DEAD, F_REPRODUCED, F_KILLED, F_ATE_SUPER, F_INTER_KILLED, F_INTRA_KILLED = 1, 2, 4, 8, 16, 32
-DQN, D3QN, PERD3QN, PPO = 0, 1, 2, 3
-KIND_BY_METHOD = {"DQN": DQN, "D3QN": D3QN, "PERD3QN": PERD3QN, "PPO": PPO}
+DQN, D3QN, PERD3QN, PPO, PERDQN = 0, 1, 2, 3, 4
+KIND_BY_METHOD = {"DQN": DQN, "D3QN": D3QN, "PERD3QN": PERD3QN, "PPO": PPO, "PERDQN": PERDQN}
 
 
 class Config(C.Structure):

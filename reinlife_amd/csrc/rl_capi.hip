@@ -328,7 +328,7 @@ int rl_run_ex(rl_world* h, const rl_brain* brains, int n_brains, int n_ticks, in
         }
     }
     for (int b = 0; b < n_brains; ++b)
-        if (brains[b].kind < RL_DQN || brains[b].kind > RL_PPO || !brains[b].packed) { rl_set_error("rl_run: brain %d invalid", b); return RL_E_INVALID; }
+        if (brains[b].kind < RL_DQN || brains[b].kind > RL_PERDQN || !brains[b].packed) { rl_set_error("rl_run: brain %d invalid", b); return RL_E_INVALID; }
     if (n_ticks == 0) return RL_OK;
     if (opts->eps_schedule_on_host && (!opts->eps_schedule || (int64_t)n_ticks * n_brains > RL_EPS_INLINE_MAX)) {
         rl_set_error("rl_run: eps_schedule_on_host needs a table of at most %d floats (got %lld)", RL_EPS_INLINE_MAX, (long long)n_ticks * n_brains);
@@ -370,7 +370,7 @@ int rl_policy_pack_weights(int kind, const float* sd, float* packed)
 int rl_policy_forward(int kind, const float* packed, const float* obs, int64_t n_rows, float* out, void* stream)
 {
     if (!packed || !obs || !out || n_rows < 0) { rl_set_error("rl_policy_forward: bad argument"); return RL_E_INVALID; }
-    if (kind < RL_DQN || kind > RL_PPO) { rl_set_error("rl_policy_forward: unknown brain kind %d", kind); return RL_E_INVALID; }
+    if (kind < RL_DQN || kind > RL_PERDQN) { rl_set_error("rl_policy_forward: unknown brain kind %d", kind); return RL_E_INVALID; }
     if (n_rows == 0) return RL_OK;
     DeviceGuard guard(device_of_pointer(obs));
     return rl_policy_forward_impl(kind, packed, obs, n_rows, out, (hipStream_t)stream);
@@ -384,7 +384,7 @@ int rl_policy_act(rl_world* h, const rl_brain* brains, int n_brains, const float
     if (!brains || !obs || !actions || !work) { rl_set_error("rl_policy_act: null argument"); return RL_E_INVALID; }
     if (n_brains != h->cfg.n_brains) { rl_set_error("rl_policy_act: n_brains %d != config %d", n_brains, h->cfg.n_brains); return RL_E_INVALID; }
     for (int b = 0; b < n_brains; ++b)
-        if (brains[b].kind < RL_DQN || brains[b].kind > RL_PPO || !brains[b].packed) { rl_set_error("rl_policy_act: brain %d invalid", b); return RL_E_INVALID; }
+        if (brains[b].kind < RL_DQN || brains[b].kind > RL_PERDQN || !brains[b].packed) { rl_set_error("rl_policy_act: brain %d invalid", b); return RL_E_INVALID; }
     return rl_policy_act_impl(h, brains, n_brains, obs, actions, out_q, work, (hipStream_t)stream);
 }
 

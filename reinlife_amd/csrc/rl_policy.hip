@@ -5,7 +5,8 @@
 //   D3QN     dueling_ddqn.forward    D3QN.py:161-165     153 -> 128 -> (128 -> 8 || 128 -> 1), q = adv + val - mean(adv)
 //   PERD3QN  DuelingDDQN.forward     PERD3QN.py:198-202  (same network)
 //   PPO      PPO.pi                  PPO.py:101-106      153 -> 256 -> 256 -> 8 -> softmax
-//   action selection                 DQN.py:132-139, D3QN.py:167-173, PERD3QN.py:204-210, PPO.py:164-169
+//   PERDQN   DQN.forward             PERDQN.py:311-323   153 -> 64 -> 64 -> 8
+//   action selection                 DQN.py:132-139, D3QN.py:167-173, PERD3QN.py:204-210, PPO.py:164-169, PERDQN.py:101-111
 // The reference runs one batch-1 forward per agent; here 32 agents of one brain form a tile computed by TWO waves on one SIMD (the tiles of
 // the multi-tick kernel's policy half, rl_policy_dev.h): k_policy_pair = four tiles of one brain per 512-thread workgroup, k_policy_dense
 // from 1,536 dueling tiles on; k_policy_wave (policy_variant "wave") = one wave per tile.  One arithmetic in all of them:
@@ -37,7 +38,7 @@ struct BrainSlot {
     const int* rowlist;    // row ids (world*cap + k) of the agents using this brain; nullptr = dense rows 0..n_rows-1
     const int* count_ptr;  // device count of rowlist entries (nullptr = n_rows)
     float eps;
-    int kind;              // RL_DQN .. RL_PPO (read by the mixed-kind launch only)
+    int kind;              // RL_DQN .. RL_PERDQN (read by the mixed-kind launch only)
 };
 
 struct PolicyArgs {
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(64 * kDenseTiles, 2) void k_policy_dense(const Poli
 }
 
 // policy_variant "pair" (the default stand-alone launch): TWO waves per 32-row tile -- policy_tile1s<PAIR> for the dueling kinds,
-// policy_pair2 for DQN / PPO: the tiles (and the arithmetic) of the multi-tick kernel's policy half, for brains of any kinds.
+// policy_pair2 for DQN / PPO, policy_pair_perdqn for PERDQN: the tiles (and the arithmetic) of the multi-tick kernel's policy half, for brains of any kinds.
 // A workgroup is what k_run's policy half is: kPairTiles tiles of ONE brain on 2 * kPairTiles waves, tile t on waves t and t + kPairTiles --
 // for four tiles the two roles of a tile share a SIMD (waves i and i + 4 do: tools/ubench/simd_map.hip), which is what the pair was
 // scheduled for: a role alone on its SIMD issues a VALU instruction every 8 cycles, two fill each other's waits.  With
@@ -212,7 +213,7 @@ __global__ __launch_bounds__(128 * kPairTiles) void k_policy_pair(const PolicyAr
             }
         }
         gfloat* pk = (gfloat*)B.packed;   // (the brain's epilogue / head constants meanwhile)
-        for (int i = tid; i < tile_const_floats(kind); i += 128 * kPairTiles) lds_c[i] = pk[tile_const_src(kind, i)];
+        for (int i = tid; i < pair_const_floats(kind); i += 128 * kPairTiles) lds_c[i] = pk[pair_const_src(kind, i)];
         if (have) {
 #pragma unroll
             for (int rr = 0; rr < 16; ++rr) {
@@ -228,12 +229,14 @@ __global__ __launch_bounds__(128 * kPairTiles) void k_policy_pair(const PolicyAr
     if (have) {
         if (kind == RL_DQN) policy_pair2<RL_DQN, false>(io, lane, role, &pl, &part);
         else if (kind == RL_PPO) policy_pair2<RL_PPO, false>(io, lane, role, &pl, &part);
+        else if (kind == RL_PERDQN) policy_pair_perdqn(io, lane, role, &pl, &part);
         else policy_tile1s<RL_PERD3QN, false, true>(io, lane, role, &pl, &part);
     } else { lds_barrier(); lds_barrier(); }   // (the two exchanges inside a tile)
     lds_barrier();
     if (have && role == 0) {
         if (kind == RL_DQN) pair_finish<RL_DQN>(io, lane, part, &pl);
         else if (kind == RL_PPO) pair_finish<RL_PPO>(io, lane, part, &pl);
+        else if (kind == RL_PERDQN) pair_finish<RL_PERDQN>(io, lane, part, &pl);
         else tile1_finish<RL_PERD3QN>(io, lane, part.head, pl.val[j], part.draw, *(const f32x4*)(lds_c + 768 + 8 + 4 * (lane >> 5)));
     }
 }
@@ -282,15 +285,16 @@ int64_t rl_policy_n_params_impl(int kind)
     if (kind == RL_DQN) return 153 * 128 + 128 + 128 * 64 + 64 + 64 * 8 + 8;
     if (kind == RL_D3QN || kind == RL_PERD3QN) return 153 * 128 + 128 + 2 * (128 * 128 + 128) + 128 * 8 + 8 + 128 + 1;
     if (kind == RL_PPO) return 153 * 256 + 256 + 256 * 256 + 256 + 256 * 8 + 8 + 256 + 1;
+    if (kind == RL_PERDQN) return 153 * 64 + 64 + 64 * 64 + 64 + 64 * 8 + 8;
     return -1;
 }
 int64_t rl_policy_packed_floats_impl(int kind)
 {
-    if (kind < RL_DQN || kind > RL_PPO) return -1;
+    if (kind < RL_DQN || kind > RL_PERDQN) return -1;
     return layout_of(kind).total;
 }
 
-// ---- f16 split of a scaled weight (host mirror of split_pair): hi = x toward zero, lo = x - hi toward zero ----
+// ---- f16 split of a scaled weight (host side of split_pair) ----
 static inline uint16_t f16_rtz(float f)  // |f| < 65504 (scaled weights are < 2^12), result exact toward zero
 {
     uint32_t u;
@@ -311,10 +315,29 @@ static inline float f16_to_float(uint16_t h)
     memcpy(&f, &u, 4);
     return f;
 }
-static inline void split2_host(float x, uint16_t (&out)[2])
+static inline uint16_t f16_rne(float f)  // |f| < 65504, rounded to the nearest f16, ties to even (subnormals included)
 {
-    out[0] = f16_rtz(x);
-    out[1] = f16_rtz(x - f16_to_float(out[0]));
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    const uint32_t sign = (u >> 16) & 0x8000u;
+    const int e = (int)((u >> 23) & 0xff) - 127;
+    if (e < -25) return (uint16_t)sign;                                       // below half the smallest subnormal
+    const int eq = e < -14 ? -14 : e;                                         // exponent of the f16 quantum 2^(eq - 10)
+    const int shift = 13 + (eq - e);
+    const uint32_t man = (u & 0x7fffffu) | 0x800000u;
+    uint32_t r = man >> shift;
+    const uint32_t rem = man & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    if (rem > half || (rem == half && (r & 1u))) ++r;                         // (a carry into the exponent is the right result)
+    return (uint16_t)(sign | (uint32_t)(((eq + 14) << 10) + r));
+}
+// hi = x toward zero, lo = x - hi toward zero (the four kinds of the multi-tick kernel, whose packed bits are fixed); rne: both parts to
+// the nearest f16 (PERDQN) -- truncating twice shrinks every weight by up to 2^-20 of itself, always toward zero, and on PERDQN's trained
+// checkpoints, whose Q values are differences of large terms, that bias alone made the forward 2.5x less exact than an f32 one
+static inline void split2_host(float x, uint16_t (&out)[2], bool rne)
+{
+    out[0] = rne ? f16_rne(x) : f16_rtz(x);
+    const float rest = x - f16_to_float(out[0]);   // (exact)
+    out[1] = rne ? f16_rne(rest) : f16_rtz(rest);
 }
 // scale of output feature o of a row-major [n_out][n_in] matrix: 2^(kScaleExp - exponent(max |W[o][:]|))
 static void feature_scales(const float* W, int n_out, int n_in, std::vector<float>& sc, std::vector<float>& un)
@@ -338,7 +361,7 @@ static void write_epilogue_consts(float* consts, int tout, const std::vector<flo
             }
 }
 
-static void pack_in_layer(const float* W, const float* b, int n_out, float* dst)
+static void pack_in_layer(const float* W, const float* b, int n_out, float* dst, bool rne = false)
 {
     // dst16[c][t][plane][lane][e] = part_plane(scale[o] * W[o = 32t + (lane&31)][k = 16c + 8(lane>>5) + e]), zero for k >= 153
     const int tout = n_out / 32;
@@ -351,12 +374,12 @@ static void pack_in_layer(const float* W, const float* b, int n_out, float* dst)
                 for (int e = 0; e < 8; ++e) {
                     const int o = 32 * t + (lane & 31), k = 16 * c + 8 * (lane >> 5) + e;
                     uint16_t parts[2];
-                    split2_host(k < 153 ? W[(size_t)o * 153 + k] * sc[o] : 0.0f, parts);
+                    split2_host(k < 153 ? W[(size_t)o * 153 + k] * sc[o] : 0.0f, parts, rne);
                     for (int pl = 0; pl < kPlanes; ++pl) d16[(((((size_t)c * tout + t) * kPlanes + pl) * 64 + lane) * 8) + e] = parts[pl];
                 }
     write_epilogue_consts(dst + frag_floats(kInChunks, tout), tout, un, b);
 }
-static void pack_hidden_layer(const float* W, const float* b, int n_in, int n_out, float* dst)
+static void pack_hidden_layer(const float* W, const float* b, int n_in, int n_out, float* dst, bool rne = false)
 {
     // dst16[s = t*2+c][t2][plane][lane][e] = part_plane(scale[o] * W[o = 32 t2 + (lane&31)][32 t + (r&3) + 8(r>>2) + 4(lane>>5)]), r = 8c + e
     const int tin = n_in / 32, tout = n_out / 32;
@@ -371,13 +394,13 @@ static void pack_hidden_layer(const float* W, const float* b, int n_in, int n_ou
                         const int r = 8 * c + e;
                         const int o = 32 * t2 + (lane & 31), k = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                         uint16_t parts[2];
-                        split2_host(W[(size_t)o * n_in + k] * sc[o], parts);
+                        split2_host(W[(size_t)o * n_in + k] * sc[o], parts, rne);
                         const size_t sidx = (size_t)t * 2 + c;
                         for (int pl = 0; pl < kPlanes; ++pl) d16[((((sidx * tout + t2) * kPlanes + pl) * 64 + lane) * 8) + e] = parts[pl];
                     }
     write_epilogue_consts(dst + frag_floats(2 * tin, tout), tout, un, b);
 }
-static void pack_head(const float* W, const float* b, int n_in, int n_out, float* dst)
+static void pack_head(const float* W, const float* b, int n_in, int n_out, float* dst, bool rne = false)
 {
     // dst16[t][c][plane][lane][e] = part_plane(scale[o] * W[o = lane&31][32 t + (r&3) + 8(r>>2) + 4(lane>>5)]), r = 8c + e, rows
     // >= n_out are zero; then unscale[8] (1 for unused outputs), then bias[8] (0 for unused outputs)
@@ -391,7 +414,7 @@ static void pack_head(const float* W, const float* b, int n_in, int n_out, float
                 for (int e = 0; e < 8; ++e) {
                     const int r = 8 * c + e, o = lane & 31, k = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                     uint16_t parts[2];
-                    split2_host(o < n_out ? W[(size_t)o * n_in + k] * sc[o] : 0.0f, parts);
+                    split2_host(o < n_out ? W[(size_t)o * n_in + k] * sc[o] : 0.0f, parts, rne);
                     for (int pl = 0; pl < kPlanes; ++pl) d16[(((((size_t)t * 2 + c) * kPlanes + pl) * 64 + lane) * 8) + e] = parts[pl];
                 }
     float* consts = dst + head_consts_off(tin);
@@ -400,7 +423,7 @@ static void pack_head(const float* W, const float* b, int n_in, int n_out, float
 
 int rl_policy_pack_impl(int kind, const float* sd, float* packed)
 {
-    if (kind < RL_DQN || kind > RL_PPO) { rl_set_error("unknown brain kind %d", kind); return RL_E_INVALID; }
+    if (kind < RL_DQN || kind > RL_PERDQN) { rl_set_error("unknown brain kind %d", kind); return RL_E_INVALID; }
     const Layout L = layout_of(kind);
     const float* p = sd;
     if (kind == RL_DQN) {
@@ -413,10 +436,14 @@ int rl_policy_pack_impl(int kind, const float* sd, float* packed)
         pack_head(p, p + 128 * 8, 128, 8, packed + L.ha); p += 128 * 8 + 8;
         pack_hidden_layer(p, p + 128 * 128, 128, 128, packed + L.l2b); p += 128 * 128 + 128;
         pack_head(p, p + 128, 128, 1, packed + L.hb);
-    } else {
+    } else if (kind == RL_PPO) {
         pack_in_layer(p, p + 153 * 256, 256, packed + L.l1); p += 153 * 256 + 256;
         pack_hidden_layer(p, p + 256 * 256, 256, 256, packed + L.l2a); p += 256 * 256 + 256;
         pack_head(p, p + 256 * 8, 256, 8, packed + L.ha);  // fc_v is not evaluated when acting (PPO.py:164-169)
+    } else {   // PERDQN: fc.0, fc.2, fc.4 -- split to the nearest (split2_host)
+        pack_in_layer(p, p + 153 * 64, 64, packed + L.l1, true); p += 153 * 64 + 64;
+        pack_hidden_layer(p, p + 64 * 64, 64, 64, packed + L.l2a, true); p += 64 * 64 + 64;
+        pack_head(p, p + 64 * 8, 64, 8, packed + L.ha, true);
     }
     return RL_OK;
 }
@@ -433,7 +460,8 @@ static int policy_grid(int64_t max_rows)  // tiles one brain can have: one 4-wav
 // hi.lo, hi.hi, lo.hi of every 16-k chunk in chunk order into ONE f32 accumulator, heads as three product chains joined at the end
 // (policy_tile1 / policy_tile1s / policy_tile1ds for the dueling kinds, policy_pair2 for DQN and PPO) -- so rl_policy_act + rl_tick,
 // rl_run, one GPU or eight, 256 worlds or 4096 give the same Q values, probabilities and actions BIT FOR BIT:
-//   pair    k_policy_pair: two waves per 32-row tile, brains of any kinds in one launch (the default below 1,536 tiles, and for DQN / PPO)
+//   pair    k_policy_pair: two waves per 32-row tile, brains of any kinds in one launch (the default below 1,536 tiles, and for DQN / PPO /
+//           PERDQN, whose tile exists only here)
 //   dense   k_policy_dense: four one-wave tiles of one dueling brain per workgroup, weights through LDS -- the same bits as `pair` for
 //           the dueling kinds; the default from 1,536 tiles on (2,048 / 4,096 / 10,880 tiles: 32.4 / 60.9 / 148 us against 38.6 / 72.7 /
 //           188 for the 4-wave tile)
@@ -493,7 +521,7 @@ static int launch_policy(int variant, int kind, const PolicyArgs& a, int64_t max
 
 int rl_policy_forward_impl(int kind, const float* packed, const float* obs, int64_t n_rows, float* out, hipStream_t st)
 {
-    if (kind < RL_DQN || kind > RL_PPO) { rl_set_error("unknown brain kind %d", kind); return RL_E_INVALID; }
+    if (kind < RL_DQN || kind > RL_PERDQN) { rl_set_error("unknown brain kind %d", kind); return RL_E_INVALID; }
     PolicyArgs a{};
     a.nb = 1; a.b[0].packed = packed; a.b[0].kind = kind; a.obs = obs; a.n_rows = n_rows; a.out = out; a.cap = 1;
     return launch_policy(resolve_variant(rl_options_current().policy_variant, kind_is_dueling(kind), n_rows), kind, a, n_rows, n_rows, st);
@@ -548,7 +576,7 @@ int rl_policy_act_impl(rl_world* h, const rl_brain* brains, int n_brains, const 
         return s;
     };
     for (int b = 0; b < n_brains; ++b)
-        if (brains[b].kind < RL_DQN || brains[b].kind > RL_PPO) { rl_set_error("unknown brain kind %d", brains[b].kind); return RL_E_INVALID; }
+        if (brains[b].kind < RL_DQN || brains[b].kind > RL_PERDQN) { rl_set_error("unknown brain kind %d", brains[b].kind); return RL_E_INVALID; }
     bool all_dueling = true;
     for (int b = 0; b < n_brains; ++b) all_dueling = all_dueling && kind_is_dueling(brains[b].kind);
     const int variant = resolve_variant(h->opt.policy_variant, all_dueling, expected);

@@ -5,7 +5,8 @@
 //   D3QN     dueling_ddqn.forward    D3QN.py:161-165     153 -> 128 -> (128 -> 8 || 128 -> 1), q = adv + val - mean(adv)
 //   PERD3QN  DuelingDDQN.forward     PERD3QN.py:198-202  (same network)
 //   PPO      PPO.pi                  PPO.py:101-106      153 -> 256 -> 256 -> 8 -> softmax
-//   action selection                 DQN.py:132-139, D3QN.py:167-173, PERD3QN.py:204-210, PPO.py:164-169
+//   PERDQN   DQN.forward             PERDQN.py:311-323   153 -> 64 -> 64 -> 8 (the stand-alone policy launches only: policy_pair_perdqn)
+//   action selection                 DQN.py:132-139, D3QN.py:167-173, PERD3QN.py:204-210, PPO.py:164-169, PERDQN.py:101-111
 // The reference runs one batch-1 forward per agent; here 32 agents (observation rows) of one brain form a TILE, and a tile is computed by
 // TWO waves that share a SIMD (policy_tile1s<PAIR> for the dueling kinds, policy_pair2 for DQN / PPO: each role owns half of every layer's
 // output features, the halves meet through LDS twice per tile) -- inside the multi-tick kernel (k_run's policy half: up to four tiles of a
@@ -63,7 +64,8 @@ __host__ __device__ constexpr int64_t head_floats(int tin, int nout) { return he
 struct Layout {  // offsets (floats) into a brain's packed buffer
     int64_t l1, l2a, l2b, ha, hb, total;
 };
-__host__ __device__ inline Layout layout_of(int kind)
+// run_layout_of: the four kinds the multi-tick kernel runs (k_run reads it with a RUNTIME kind: tile_const_src); layout_of: every kind
+__host__ __device__ inline Layout run_layout_of(int kind)
 {
     Layout L{};
     int64_t o = 0;
@@ -82,6 +84,17 @@ __host__ __device__ inline Layout layout_of(int kind)
         L.l2a = o; o += hid_layer_floats(8, 8);
         L.ha = o; o += head_floats(8, 8);
     }
+    L.total = o;
+    return L;
+}
+__host__ __device__ inline Layout layout_of(int kind)
+{
+    if (kind != RL_PERDQN) return run_layout_of(kind);
+    Layout L{};
+    int64_t o = 0;
+    L.l1 = o; o += in_layer_floats(2);
+    L.l2a = o; o += hid_layer_floats(2, 2);
+    L.ha = o; o += head_floats(2, 8);
     L.total = o;
     return L;
 }
@@ -1467,10 +1480,10 @@ __host__ __device__ constexpr int tile_const_floats(int kind)
     return kind == RL_DQN ? 256 + 128 + 16 : kind == RL_PPO ? 512 + 512 + 16 : 3 * 256 + 2 * 16;
 }
 constexpr int kTileConstMax = 512 + 512 + 16;
-// element j of a brain's LDS constant block -> offset in its packed weights
+// element j of a brain's LDS constant block -> offset in its packed weights (the kinds of k_run; the stand-alone pair kernel: pair_const_src)
 __host__ __device__ inline int64_t tile_const_src(int kind, int j)
 {
-    const Layout L = layout_of(kind);
+    const Layout L = run_layout_of(kind);
     if (kind == RL_DQN) {
         if (j < 256) return L.l1 + frag_floats(kInChunks, 4) + j;
         if (j < 384) return L.l2a + frag_floats(8, 2) + (j - 256);
@@ -1486,6 +1499,16 @@ __host__ __device__ inline int64_t tile_const_src(int kind, int j)
     if (j < 768) return L.l2b + frag_floats(8, 4) + (j - 512);
     if (j < 784) return L.ha + head_consts_off(4) + (j - 768);
     return L.hb + head_consts_off(4) + (j - 784);
+}
+// ... and with PERDQN, whose tile only the stand-alone pair kernel runs: [input layer 128 | hidden layer 128 | head 16]
+__host__ __device__ constexpr int pair_const_floats(int kind) { return kind == RL_PERDQN ? 128 + 128 + 16 : tile_const_floats(kind); }
+__host__ __device__ inline int64_t pair_const_src(int kind, int j)
+{
+    if (kind != RL_PERDQN) return tile_const_src(kind, j);
+    const Layout L = layout_of(RL_PERDQN);
+    if (j < 128) return L.l1 + frag_floats(kInChunks, 2) + j;
+    if (j < 256) return L.l2a + frag_floats(4, 2) + (j - 128);
+    return L.ha + head_consts_off(2) + (j - 256);
 }
 __host__ __device__ constexpr int pair_ex_bytes(int kind) { return (kind == RL_PPO ? 16 : 8) * kPlanes * 64 * 16; }
 constexpr int kPairValFloats = 256;   // role 1's head partials: 4 per lane
@@ -1739,7 +1762,7 @@ template <int KIND>
 __device__ inline void pair_finish(const TileIO& io, int lane, const Tile1Part& part, const PairLds* pair_lds)
 {
     extern __shared__ __attribute__((aligned(16))) char rl_dyn_lds[];
-    constexpr int T1 = KIND == RL_PPO ? 8 : 4;
+    constexpr int T1 = KIND == RL_PPO ? 8 : KIND == RL_PERDQN ? 2 : 4;
     const int h = lane >> 5;
     const float* const hconsts = (const float*)(rl_dyn_lds + io.c_lds_off) + T1 * 64 + (KIND == RL_PPO ? 512 : 128);
     const f32x4 other = *(const f32x4*)(pair_lds->val + 4 * lane), bias = *(const f32x4*)(hconsts + 8 + 4 * h);
@@ -1784,6 +1807,161 @@ __device__ inline void pair_finish(const TileIO& io, int lane, const Tile1Part& 
                 if (io.lds_actions_off >= 0) ((signed char*)rl_dyn_lds)[io.lds_actions_off + io.lds_slot] = (signed char)a;
             }
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// PERDQN (PERDQN.py:311-325: 153 -> 64 -> 64 -> 8) on the pair protocol of policy_pair2<RL_DQN>, finished by pair_finish<RL_PERDQN>:
+//   input layer   role r: output tile r (one tile, K = 160: 10 chunks x 3 MFMAs into three chains hi.lo / hi.hi / lo.hi, the next chunk
+//                 split in their shadows, as head_stream does);
+//   hidden layer  role r: output tile r over the 4 K-chunks of both roles' split activations (main / cross chains, as DQN's);
+//   head          role r: its own K-chunks 2r, 2r+1 with its own row factor; role 1's partials cross through pair_lds->val.
+// 96 MFMAs per tile (30 + 12 + 6 per role) against DQN's 180.  The stand-alone policy launches only: k_run has no PERDQN tile.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ inline void policy_pair_perdqn(const TileIO& io, int lane, int role, const PairLds* pair_lds, Tile1Part* part)
+{
+    extern __shared__ __attribute__((aligned(16))) char rl_dyn_lds[];
+    constexpr int D = 3;
+    const int h = lane >> 5;
+    const Layout L = layout_of(RL_PERDQN);
+    gfloat* __restrict__ packed = io.packed;
+    const float* const cbase = (const float*)(rl_dyn_lds + io.c_lds_off);
+    const float* const c1 = cbase + 32 * h;                 // input layer: [tile][half][unscale 16 | bias 16]
+    const float* const c2 = cbase + 2 * 64 + 32 * h;        // hidden layer
+    const float* const hconsts = cbase + 4 * 64;            // head: [unscale 8 | bias 8]
+    WRing<2, 1, 1, D> w1;
+    w1.start(packed + L.l1, lane, role);
+    f32x4 X[kInChunks][2];
+    if (io.x_lds_off >= 0) {
+        const float* xr = (const float*)(rl_dyn_lds + io.x_lds_off);
+#pragma unroll
+        for (int c = 0; c < kInChunks; ++c)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                if (c == kInChunks - 1 && h == 1) X[c][q] = f32x4{xr[149], xr[150], xr[151], xr[152]};
+                else X[c][q] = *(const f32x4*)(xr + 16 * c + 8 * h + 4 * q);
+            }
+    } else {
+        const int64_t rbase = io.row * RL_OBS_DIM;
+#pragma unroll
+        for (int c = 0; c < kInChunks; ++c)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) X[c][q] = *(const f32x4u*)(io.obs + rbase + ((c == kInChunks - 1 && h == 1) ? 149 : 16 * c + 8 * h + 4 * q));
+    }
+    rl_u4 draw = {0u, 0u, 0u, 0u};
+    if (role == 0 && io.actions && io.eps > 0.0f)
+        draw = rl_philox4x32(io.seed, io.key_epoch, io.key_world, io.key_tick, RL_SITE_ACT, io.key_index);
+    if (h == 1) { X[kInChunks - 1][0] = f32x4{X[kInChunks - 1][0].w, 0.0f, 0.0f, 0.0f}; X[kInChunks - 1][1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
+    float sc0, un0;
+    {
+        float m4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int c = 0; c < kInChunks; ++c)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                max3_abs(m4[(2 * c + q) & 3], X[c][q].x, X[c][q].y);
+                max3_abs(m4[(2 * c + q + 2) & 3], X[c][q].z, X[c][q].w);
+            }
+        float m = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
+        m = fmaxf(m, __shfl_xor(m, 32));
+        row_scale(m, sc0, un0);
+    }
+    // ---- input layer 153 -> 64: output tile `role`
+    f32x16 F;
+    {
+        auto xraw = [&](int c, int e) { return X[c][e >> 2][e & 3]; };
+        f32x16 a0, a1, a2;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { a0[r] = 0.0f; a1[r] = 0.0f; a2[r] = 0.0f; }
+        f32x4 B1[kInChunks][kPlanes];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) split_slice<3>(k, [&](int e) { return xraw(0, e); }, sc0, B1[0][0], B1[0][1]);
+#pragma unroll
+        for (int s = 0; s < kInChunks; ++s) {
+            f32x4 ac[1][kPlanes];
+            w1.template next<kInChunks>(s, ac);
+            a0 = mfma16(ac[0][0], B1[s][1], a0);   // hi.lo
+            if (s + 1 < kInChunks) split_slice<3>(0, [&](int e) { return xraw(s + 1, e); }, sc0, B1[s + 1][0], B1[s + 1][1]);
+            __builtin_amdgcn_sched_barrier(0);
+            a1 = mfma16(ac[0][0], B1[s][0], a1);   // hi.hi
+            if (s + 1 < kInChunks) split_slice<3>(1, [&](int e) { return xraw(s + 1, e); }, sc0, B1[s + 1][0], B1[s + 1][1]);
+            __builtin_amdgcn_sched_barrier(0);
+            a2 = mfma16(ac[0][1], B1[s][0], a2);   // lo.hi
+            if (s + 1 < kInChunks) split_slice<3>(2, [&](int e) { return xraw(s + 1, e); }, sc0, B1[s + 1][0], B1[s + 1][1]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) F[r] = (a0[r] + a1[r]) + a2[r];
+    }
+    // (the hidden layer's and the head's first weight chunks are requested before the epilogue and the two exchanges)
+    WRing<2, 1, 1, D> w2;
+    w2.start(packed + L.l2a, lane, role);
+    WRing<1, 1, 1, 2> wh;
+    wh.start(packed + L.ha, lane, 2 * role);
+    EpiStream ep;
+    float mrow = 0.0f;
+    {
+        f32x16 dummy = F;
+        ep.c = c1 + role * 64;
+        ep.fetch(0, 0);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) ep.step(0, e, F, dummy, un0, mrow);
+    }
+    // ---- the row's scale over both roles' features, then the split activations of both roles through LDS
+    mrow = fmaxf(mrow, __shfl_xor(mrow, 32));
+    pair_lds->pmax[role * 64 + lane] = mrow;
+    lds_barrier();
+    mrow = fmaxf(mrow, pair_lds->pmax[(role ^ 1) * 64 + lane]);
+    float sc1, un1;
+    row_scale(mrow, sc1, un1);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {   // own chunks: registers 8c .. 8c + 7 of own tile = chunk 2 role + c of the layer
+        f32x4 hi, lo;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) split_slice<6>(k, [&](int e) { return F[8 * c + e]; }, sc1, hi, lo);
+        pair_lds->ex[((2 * role + c) * kPlanes + 0) * 64 + lane] = hi;
+        pair_lds->ex[((2 * role + c) * kPlanes + 1) * 64 + lane] = lo;
+    }
+    lds_barrier();
+    // ---- hidden layer 64 -> 64: output tile `role`
+    f32x4 B2[4][kPlanes];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int pl = 0; pl < kPlanes; ++pl) B2[c][pl] = pair_lds->ex[(c * kPlanes + pl) * 64 + lane];
+    f32x16 acc, cross;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[r] = 0.0f; cross[r] = 0.0f; }
+#pragma unroll
+    for (int s2 = 0; s2 < 4; ++s2) {
+        f32x4 ac[1][kPlanes];
+        w2.template next<4>(s2, ac);
+        cross = mfma16(ac[0][0], B2[s2][1], cross);   // hi.lo
+        acc = mfma16(ac[0][0], B2[s2][0], acc);       // hi.hi
+        cross = mfma16(ac[0][1], B2[s2][0], cross);   // lo.hi
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] += cross[r];
+    float head4[4];
+    {
+        f32x16 dummy = acc;
+        float m2 = 0.0f;
+        ep.c = c2 + role * 64;
+        ep.fetch(0, 0);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) ep.step(0, e, acc, dummy, un1, m2);
+        m2 = fmaxf(m2, __shfl_xor(m2, 32));
+        float sc2, un2;
+        row_scale(m2, sc2, un2);
+        auto araw = [&](int c, int e) { return acc[8 * (c & 1) + e]; };
+        head_stream<2, 2>(wh, *(const f32x4*)(hconsts + 4 * h), araw, sc2, un2, head4);
+    }
+    if (role) *(f32x4*)(pair_lds->val + 4 * lane) = f32x4{head4[0], head4[1], head4[2], head4[3]};
+    else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part->head[r] = head4[r];
+        part->draw = draw;
     }
 }
 

@@ -1282,8 +1282,19 @@ static int run_block(const rl_world* h)
     return h->opt.run_always ? 512 : 256;
 #endif
 }
+// k_run has no PERDQN tile: such a brains list runs in the two-launch loop (rl_policy_act + rl_tick_refill), whose pair kernel has one
+static bool has_perdqn(const rl_brain* brains, int n_brains)
+{
+    for (int b = 0; b < n_brains; ++b)
+        if (brains[b].kind == RL_PERDQN) return true;
+    return false;
+}
 int rl_world_run_supported(const rl_world* h, const rl_brain* brains, int n_brains)
 {
+    if (has_perdqn(brains, n_brains)) {
+        rl_set_error("rl_run: PERDQN brains are not run by the multi-tick kernel: use the two-launch loop (rl_policy_act + rl_tick_refill)");
+        return 0;
+    }
     const int kind = run_kind_of(brains, n_brains);
     if (kind < 0) return 0;
     const int T = run_block(h);
@@ -1320,7 +1331,10 @@ int rl_world_launch_run(rl_world* h, const rl_brain* brains, int n_brains, int n
                         float* const obs[2], int first, int16_t* upd_src, int refill_threshold, int refill_n_agents,
                         int32_t* refill_count, const float* eps_sched, int eps_on_host, int trk_skip, const rl_replay* replays, float* policy_out, hipStream_t st)
 {
-    if (!rl_world_run_supported(h, brains, n_brains)) { rl_set_error("rl_run: unsupported configuration (brain kinds / slot_cap / LDS)"); return RL_E_UNSUPPORTED; }
+    if (!rl_world_run_supported(h, brains, n_brains)) {
+        if (!has_perdqn(brains, n_brains)) rl_set_error("rl_run: unsupported configuration (brain kinds / slot_cap / LDS)");
+        return RL_E_UNSUPPORTED;
+    }
     KParams p = make_params(h);
     set_list_production(h, p, false);   // the row lists describe the state BEFORE this launch
     p.actions = actions;
