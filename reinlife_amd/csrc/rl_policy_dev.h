@@ -831,10 +831,11 @@ __device__ __attribute__((noinline, cold)) void tile1_cert_fallback(TileIO io, c
     const float adv[4] = {adv4.x, adv4.y, adv4.z, adv4.w};
     tile1_finish<KIND>(io, lane, adv, val[0] + hconsts[16 + 8], draw, *(const f32x4*)(hconsts + 8 + 4 * h));
 }
-// Role 0's finish without V: vbar >= |v| of the lane's row (see above), ex / un1 what the fallback needs.
-template <int KIND>
+// The finish without V: vbar >= |v| of the lane's row (see above); fallback(): what runs the value branch after all and finishes the tile
+// (the pair tile: tile1_cert_fallback on role 0; the one-wave tile: the whole full tile again, tile1s_full_cold).
+template <int KIND, typename Fallback>
 __device__ inline void tile1_finish_cert(const TileIO& io, int lane, const float (&adv)[4], const rl_u4& draw, const float* hconsts, float vbar,
-                                         const f32x4* ex, float un1)
+                                         Fallback&& fallback)
 {
     const int h = lane >> 5;
     const f32x4 ba = *(const f32x4*)(hconsts + 8 + 4 * h);
@@ -865,7 +866,7 @@ __device__ inline void tile1_finish_cert(const TileIO& io, int lane, const float
     const bool need = greedy && !ok;
     RL_CERT_COUNT(__ballot(greedy), __ballot(greedy && ok), __any(need));
     if (__builtin_expect(__any(need), 0)) {   // (wave-uniform)
-        tile1_cert_fallback<KIND>(io, ex, un1, f32x4{adv[0], adv[1], adv[2], adv[3]}, draw);
+        fallback();
         return;
     }
     if (h == 0 && io.valid && io.actions) {
@@ -914,11 +915,16 @@ __device__ inline float f32_up(double d)
     return f;
 }
 
+// The certified ONE-WAVE tile's fallback: the whole full tile again, out of line -- it carries no state over (the rows are
+// still in the mirror or in memory, the Philox draw comes from the same keys), so the hot tile's register allocation is that of the
+// certified path alone.
+template <int KIND, bool COHERENT, int XM>
+__device__ __attribute__((noinline, cold)) void tile1s_full_cold(TileIO io);
+
 template <int KIND, bool COHERENT, bool PAIR = false, int XM = 0, bool CERT = false>   // XM: what is known about the rows (in_chunk_class): 0 nothing, 1 RL_XF_SCALE, 2 + RL_XF_INT_HEALTH
 __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, const PairLds* pair_lds = nullptr, Tile1Part* part = nullptr)
 {
     static_assert(KIND == RL_D3QN || KIND == RL_PERD3QN, "one-wave tile: dueling kinds");
-    static_assert(!CERT || PAIR, "the certified argmax: the pair tile");
     extern __shared__ __attribute__((aligned(16))) char rl_dyn_lds[];
     constexpr int D = 3;
     const int h = lane >> 5;
@@ -1051,6 +1057,7 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
 #pragma unroll
         for (int e = 0; e < 32; ++e) ep.step(2, e, F[2], F[3], un0, mrow);
         mrow = fmaxf(mrow, __shfl_xor(mrow, 32));
+        zrow = mrow;
         row_scale(mrow, sc1, un1);
         // relu(feature) feeds both branches (PERD3QN.py:200-201): B2 chunk 2t + c = registers 8c .. 8c+7 of tile t
 #pragma unroll
@@ -1085,7 +1092,8 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
         head_stream<D>(wh, *(const f32x4*)(hconsts + ((PAIR && role) ? 16 : 0) + 4 * h), araw, sc2, un2, adv);
         if constexpr (CERT) {   // role 0 (role 1 left after the exchange): the action without V, or the value branch after all
             const float* const kc = hconsts + kTileConstFloats - 768;
-            tile1_finish_cert<KIND>(io, lane, adv, draw, hconsts, __builtin_fmaf(kc[1], zrow, kc[0]), pair_lds->ex, un1);
+            tile1_finish_cert<KIND>(io, lane, adv, draw, hconsts, __builtin_fmaf(kc[1], zrow, kc[0]),
+                                    [&]() { tile1_cert_fallback<KIND>(io, pair_lds->ex, un1, f32x4{adv[0], adv[1], adv[2], adv[3]}, draw); });
             RL_PMARK1(9);
             return;
         }
@@ -1099,6 +1107,12 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
         return;
     }
     head_stream<D>(wh, *(const f32x4*)(hconsts + 4 * h), araw, sc2, un2, adv);
+    if constexpr (CERT) {   // the action without V (tile1_finish_cert) -- or, for a tile with a greedy row that fails the test, the full tile
+        const float* const kc = hconsts + kTileConstFloats - 768;
+        tile1_finish_cert<KIND>(io, lane, adv, draw, hconsts, __builtin_fmaf(kc[1], zrow, kc[0]), [&]() { tile1s_full_cold<KIND, COHERENT, XM>(io); });
+        RL_PMARK1(9);
+        return;
+    }
     WRingH<8, D> w3;   // (started before the head its twelve fragments are spilled and reloaded inside the value branch's MFMA stream)
     w3.start(packed + L.l2b, lane);
     RL_PMARK1(7);
@@ -1120,6 +1134,12 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
     head_stream<D>(wh, *(const f32x4*)(hconsts + 16 + 4 * h), araw, sc2, un2, val);
     RL_PMARK1(9);
     tile1_finish<KIND>(io, lane, adv, val[0] + hconsts[16 + 8], draw, *(const f32x4*)(hconsts + 8 + 4 * h));
+}
+template <int KIND, bool COHERENT, int XM>
+__device__ __attribute__((noinline, cold)) void tile1s_full_cold(TileIO io)
+{
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    policy_tile1s<KIND, COHERENT, false, XM, false>(io, lane);
 }
 
 

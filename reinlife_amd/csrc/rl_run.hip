@@ -217,8 +217,15 @@ __device__ inline RecycleRegs recycle_read(Smem& s, int n)
 // written in here any more -- its Philox keys (s.scal[S_TICK] / [S_EPOCH]) are stored before the first barrier by the caller and only
 // re-written with the same values here, its action bytes land in
 // s.action[] slots whose carried-over value nobody reads before they are overwritten (so the carry-over itself is left to the launch's
-// last tick, where the barrier stays because store_world follows) -- and every wave passes the policy half's own barriers before
+// last tick, where the barrier stays because store_world follows) -- and every wave passes the policy half's closing barrier before
 // Environment.step reads what is written here.  Kept closed when rows have to be drained to L2 first (tiles reading them from memory).
+// With one wave per tile the closing barrier is the policy half's ONLY barrier, and the invariant reads: a wave that
+// leaves this function early may run its whole tile while other waves still write here, so (a) everything a tile READS was complete
+// before this function's first barrier -- the row lists and tile descriptors (policy_lists_wave0), the mirror and the rows in memory
+// (write_observations), the Philox keys (stored by the caller, re-written here with the same values), the brains' constants (once per
+// launch) -- and (b) what a tile WRITES, s.action[k] and the action bytes in memory, nobody writes or reads in here (`open`).  Nothing
+// aliases the mirror any more (the pair tiles' exchange buffers did: the full path, which keeps its two barriers inside the tile, both
+// behind every wave's row reads).  The fallback of a certified tile reads the same rows again before its wave reaches the closing barrier.
 #ifndef RL_SEAM_OPEN
 #define RL_SEAM_OPEN 1
 #endif
@@ -412,8 +419,9 @@ __device__ inline void policy_schedule_wave0(const KParams& p, PolSmem& ps, RunP
     }
 }
 
-// The policy half of the dueling-kind kernels.  T = 512 (256 VGPRs per wave), up to four tiles: TWO waves per tile on one SIMD
-// (policy_tile1s<PAIR>); five to eight tiles: one hand-scheduled tile per wave (policy_tile1s); T = 256: one policy_tile1 per
+// The policy half of the dueling-kind kernels.  T = 512 (256 VGPRs per wave): one hand-scheduled tile per wave (policy_tile1s), certified
+// where no Q value is stored; the full path (TRAIN 2) with up to four tiles: TWO waves per tile on one SIMD
+// (policy_tile1s<PAIR>); T = 256: one policy_tile1 per
 // wave (no LDS, no barrier inside a tile), wave i takes tiles i, i + 4, ...; T = 1024 (128 VGPRs per wave): FOUR waves per tile on one SIMD
 // (policy_quad), rounds of four tiles.  Tile rows, validity and brain come from the descriptors wave 0 wrote next to the
 // row lists (policy_lists_wave0).
@@ -435,6 +443,8 @@ __device__ __forceinline__ void run_policy1(const KParams& p, Smem& s, PolSmem& 
         if (dbg & 16) ntiles = min(ntiles, 3);
     }
     const bool mirrored = ps.xmirror != nullptr && __builtin_amdgcn_readfirstlane(ps.meta[4]) != 0;
+    // the certified argmax (no V) where no Q value is stored: uniform, a constant in the product.  Tuning builds: run mask 64 = the full path
+    [[maybe_unused]] const bool cert = T == 512 && TRAIN != 2 && !(RL_RUN_DBG(ka) & 64);
     auto tile_io = [&](int ti, TileIO& io, int j) {   // j: tile row of the lane
         const int b = __builtin_amdgcn_readfirstlane(ps.tbrain[ti]);
         const int e = (unsigned short)ps.trow[ti * 32 + j], k = e & 0x7fff;
@@ -485,13 +495,11 @@ __device__ __forceinline__ void run_policy1(const KParams& p, Smem& s, PolSmem& 
             if (have && q == 0) tile1_finish<KIND>(io, lane, part.head, ql.val[j], part.draw, *(const f32x4*)((const float*)(smem_base + io.c_lds_off) + 768 + 8 + 4 * (lane >> 5)));
         }
     } else
-    if (T == 512 && ps.pairv != nullptr && ntiles <= 4 && (size_t)ps.xrows * kXStride * sizeof(float) >= 4 * (size_t)kPairExBytes) {
-        // TWO waves per tile, on the same SIMD (waves i and i + 4): policy_tile1s<PAIR>.  Where no Q value is stored (TRAIN 0 / 1) the
-        // tile certifies its argmax instead of computing V: role 1 leaves after the input layer, role 0 finishes inside
-        // the tile, and the barrier that carried V to role 0 goes away.  (Tuning builds: run mask 64 = the full path.)
+    if (T == 512 && !cert && ps.pairv != nullptr && ntiles <= 4 && (size_t)ps.xrows * kXStride * sizeof(float) >= 4 * (size_t)kPairExBytes) {
+        // TWO waves per tile, on the same SIMD (waves i and i + 4): policy_tile1s<PAIR>, role 0 the advantage branch, role 1 the value branch.
+        // The full path: where the Q values are stored (TRAIN 2), and run mask 64 of the tuning builds.
         const int role = __builtin_amdgcn_readfirstlane(wave >> 2), slot = wave & 3;
         const bool have = slot < ntiles;
-        const bool cert = TRAIN != 2 && !(RL_RUN_DBG(ka) & 64);   // (uniform; a constant in the product)
         TileIO io;
         Tile1Part part;
         PairLds pl;
@@ -499,25 +507,30 @@ __device__ __forceinline__ void run_policy1(const KParams& p, Smem& s, PolSmem& 
         pl.ex = (f32x4*)((char*)ps.xmirror + (size_t)kPairExBytes * slot);
         if (have) {
             tile_io(slot, io, j);
-            if (cert) policy_tile1s<KIND, RL_RUN_COHERENT, true, RL_XM_DUELING_KERNEL, TRAIN != 2>(io, lane, role, &pl, &part);
-            else policy_tile1s<KIND, RL_RUN_COHERENT, true, RL_XM_DUELING_KERNEL>(io, lane, role, &pl, &part);
+            policy_tile1s<KIND, RL_RUN_COHERENT, true, RL_XM_DUELING_KERNEL>(io, lane, role, &pl, &part);
         } else { lds_barrier(); lds_barrier(); }   // (the two exchanges inside the tile)
 #ifdef RL_PHASE_PROFILE
         if (p.prof && (int)blockIdx.x == p.prof_world && lane == 0) p.prof[116 + wave] = (long long)clock64();   // (128 slots)
 #endif
-        if (!cert) {
-            lds_barrier();
-            if (have && role == 0) {   // (a fresh lane index: `lane` / `j` from above the tile lived through it -- spilled in the TRAIN instantiations, a reload behind vmcnt(0) right here)
-                const int fl = rl_lane_fresh();
-                tile1_finish<KIND>(io, fl, part.head, pl.val[fl & 31], part.draw, *(const f32x4*)((const float*)(smem_base + io.c_lds_off) + 768 + 8 + 4 * (fl >> 5)));
-            }
+        lds_barrier();
+        if (have && role == 0) {   // (a fresh lane index: `lane` / `j` from above the tile lived through it -- spilled in the TRAIN instantiations, a reload behind vmcnt(0) right here)
+            const int fl = rl_lane_fresh();
+            tile1_finish<KIND>(io, fl, part.head, pl.val[fl & 31], part.draw, *(const f32x4*)((const float*)(smem_base + io.c_lds_off) + 768 + 8 + 4 * (fl >> 5)));
         }
-    } else
-    for (int ti = wave; ti < ntiles; ti += T / 64) {
-        TileIO io;
-        tile_io(ti, io, j);
-        if (T == 512) policy_tile1s<KIND, RL_RUN_COHERENT, false, RL_XM_DUELING_KERNEL>(io, lane);
-        else policy_tile1<KIND, RL_RUN_COHERENT, true>(io, lane);
+    } else {
+        // ONE wave per tile, wave i takes tiles i, i + T / 64: no barrier and no exchange inside a tile, and a wave without a tile goes
+        // straight to the closing barrier.  T = 512 where no Q value is stored: the tile certifies its argmax instead of computing V
+        //  -- up to four tiles sit on waves 0-3 = one per SIMD.
+        for (int ti = wave; ti < ntiles; ti += T / 64) {
+            TileIO io;
+            tile_io(ti, io, j);
+            if (T == 512 && cert) policy_tile1s<KIND, RL_RUN_COHERENT, false, RL_XM_DUELING_KERNEL, T == 512 && TRAIN != 2>(io, lane);
+            else if (T == 512) policy_tile1s<KIND, RL_RUN_COHERENT, false, RL_XM_DUELING_KERNEL>(io, lane);
+            else policy_tile1<KIND, RL_RUN_COHERENT, true>(io, lane);
+        }
+#ifdef RL_PHASE_PROFILE
+        if (T == 512 && p.prof && (int)blockIdx.x == p.prof_world && lane == 0) p.prof[116 + wave] = (long long)clock64();   // (arrival at the closing barrier)
+#endif
     }
 #ifdef RL_PHASE_PROFILE
     if (p.prof && (int)blockIdx.x == p.prof_world && tid == 0) p.prof[111] = (long long)clock64();

@@ -23,3 +23,5 @@ for r in range(int(sys.argv[3]) if len(sys.argv) > 3 else 3):
         env = dict(os.environ, REINLIFE_HIP_LIB=os.path.abspath(lib))
         out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True)
         print("%-40s %s" % (os.path.basename(lib), out.stdout.strip().splitlines()[-1] if out.stdout.strip() else out.stderr[-300:]), flush=True)
+        if out.returncode != 0:   # a run that failed is a finding: nothing more is started on the card
+            sys.exit("run_ab: %s ended with %d" % (os.path.basename(lib), out.returncode))

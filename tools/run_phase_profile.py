@@ -1,16 +1,17 @@
 #!/usr/bin/env python
-"""Shader-clock stamps of the policy half of the multi-tick launch (rl_run, two waves per tile: role 0 of the first tile), workgroup `world`, wave 0, last tick of a launch
-(tuning; GPU; prof build)."""
+"""Shader-clock stamps of the policy half of the multi-tick launch (rl_run, the certified one-wave tile of DESIGN.md 5.15: wave 0 = the first tile), workgroup `world`,
+last tick of a launch (tuning; GPU; prof build)."""
 import ctypes as C, os, sys
 os.environ["RL_PHASE_PROFILE"] = "1"
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from reinlife_amd import _lib
-NAMES = ["entry -> tile known (lists were built during the previous tick)", "tile entry", "observation row: 20 reads, max, scale, first split", "input layer, own tile pair (60 MFMA) + epilogue, row-max exchange, split, exchange (2 barriers)",
-         "hidden layer of the role's branch (96 MFMA), epilogue of tiles 0,1 in its shadow", "epilogue of tiles 2,3, row max, scale", "head (24 MFMA) with the split of its input",
-         "barrier (partner wave, other tiles)", "dueling combine, argmax, stores, barrier"]
-IDX = [100, 110, 101, 102, 104, 105, 106, 109, 111, 112]
+NAMES = ["entry -> tile known (lists were built during the previous tick)", "tile entry", "observation row: 20 reads, max, scale, first split",
+         "input layer, both passes (120 MFMA), epilogue of tiles 0,1 in pass 1's shadow", "epilogue of tiles 2,3, row max, scale, first split of the hidden layer's input",
+         "advantage hidden layer (96 MFMA), splits and epilogue of tiles 0,1 in its shadow", "epilogue of tiles 2,3, row max, scale", "head (24 MFMA) with the split of its input, certificate, argmax, stores",
+         "waves 1-3 (the other tiles)", "closing barrier"]
+IDX = [100, 110, 101, 102, 103, 104, 105, 106, 109, 111, 112]
 R = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 args = __import__("argparse").Namespace(worlds=R, workload=os.environ.get("RL_AB_WORKLOAD", "c4"), seed=1)
 dw = bench.make_worlds(args, 0, "cuda:0")
@@ -35,5 +36,5 @@ print("rl_run policy half, wave 0 of the sampled world, mean of %d launches, tot
 for n, v in zip(NAMES, m):
     print("   %-52s %8.0f  %5.1f%%" % (n, v, 100 * v / m.sum()))
 if wv:
-    print("cycles from entry to each wave's arrival at the barrier behind the tiles (waves 0-3: advantage role of tiles 0-3, waves 4-7: value role):")
+    print("cycles from entry to each wave's arrival at the closing barrier (waves 0-3: tiles 0-3, waves 4-7: no tile):")
     print("   ", np.mean(wv, axis=0).round(0))
