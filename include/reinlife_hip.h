@@ -264,7 +264,18 @@ int64_t rl_policy_packed_floats(int kind);
  * adv_fc1.b adv_fc2.w adv_fc2.b value_fc1.w value_fc1.b value_fc2.w value_fc2.b;  PPO: fc1.w fc1.b fc2.w fc2.b
  * fc_pi.w fc_pi.b fc_v.w fc_v.b;  PERDQN: fc.0.w fc.0.b fc.2.w fc.2.b fc.4.w fc.4.b)  ->  MFMA-fragment-major layout read by the kernels */
 int rl_policy_pack_weights(int kind, const float* state_dict_flat, float* packed);
-/* dense batch: obs [n_rows][153] (device) -> out [n_rows][8]: Q values (per-row dueling mean) or PPO probabilities */
+/* dense batch: obs [n_rows][153] (device) -> out [n_rows][8]: Q values (per-row dueling mean) or PPO probabilities.
+ * Every row is computed from that row alone (its own power-of-two scale): its outputs do not depend on the other rows of the
+ * batch, on its position in it, or on the policy_variant.
+ * Supported magnitudes: a row (and every hidden activation row it produces) whose largest |element| is 0 or lies in
+ * [2^-95, 2^103] gets f32-grade results (|error| <= 1e-5 of the row's largest |output|; scaling a row by 2^k scales the outputs
+ * of a bias-free Q network by exactly 2^k).  Outside that range the row scale is clamped: smaller rows lose precision down to
+ * all-zero inputs, larger ones overflow the f16 operands; such a row still yields an action in 0..7, sets no error flag and
+ * does not disturb the other rows.
+ * Non-finite inputs: the reference propagates NaN; these kernels do not.  Row maximum and ReLU are fmaxf, which returns the
+ * operand that is a number, so a row holding a NaN or +-Inf element leaves the first layer as an all-zero hidden row: its
+ * outputs are FINITE (the later layers' biases alone) and its action is chosen from them.  Other rows are unaffected.
+ * The same holds for rl_policy_act and the policy half of rl_run. */
 int rl_policy_forward(int kind, const float* packed, const float* obs, int64_t n_rows, float* out, void* stream);
 /* all agents of all worlds: row (w,k) uses brains[a_brain[w][k]].
  *   obs     [R][cap][153]   actions [R][cap] (written for k < n_agents[w])   out_q [R][cap][8] or NULL

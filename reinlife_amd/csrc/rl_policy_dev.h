@@ -17,9 +17,14 @@
 //   * f32-grade results from the f16 matrix pipe ("2 x f16, block-scaled"): every f32 operand row is scaled by a power
 //     of two so that its largest element lands in [2^10, 2^11) -- per observation / activation ROW (the B operand's
 //     columns) and per output FEATURE of the weights (the A operand's rows), so the scale factors leave the MFMA as one
-//     multiply per accumulator register -- and split into two f16 parts x = hi + lo (hi = x rounded toward zero to 11
-//     bits, lo = the exact remainder, again up to 11 bits: 22 bits of every operand, measured against the row
-//     maximum).  A product is hi.hi + hi.lo + lo.hi, three v_mfma_f32_32x32x16_f16 per 16 k with f32 accumulation (the
+//     multiply per accumulator register -- and split into two f16 parts x = hi + lo (hi = the scaled x as an f16, 11
+//     bits; lo = the f16 of the exact remainder, up to 11 more: 22 bits of every operand, measured against the row
+//     maximum).  Rounding: the ACTIVATIONS are split on the device to the nearest f16, ties to even, both parts
+//     (split_pair: v_fma_mix); the WEIGHTS are split on the host, both parts toward zero for DQN / D3QN / PERD3QN /
+//     PPO (whose packed bits are fixed) and to the nearest for PERDQN (split2_host, rl_policy.hip).  A row's scale
+//     comes from the biased exponent of its largest magnitude clamped to [32, 230] (row_scale): rows whose maximum
+//     lies in [2^-95, 2^103], and all-zero rows, are exact in this sense; NaN elements are dropped by the fmaxf of
+//     the row maximum and of the ReLU (include/reinlife_hip.h, rl_policy_forward).  A product is hi.hi + hi.lo + lo.hi, three v_mfma_f32_32x32x16_f16 per 16 k with f32 accumulation (the
 //     cross terms in their own accumulator); the dropped lo.lo term is 2^-22 relative.  Measured
 //     difference to the reference's torch outputs on the golden vectors: ~1e-7 (the bar is 1e-5) -- the same as an f32
 //     numpy forward.  The power-of-two scaling makes the scheme independent of the operands' magnitude (f16 alone

@@ -13,9 +13,13 @@ import numpy as np
 
 
 class PolicyCheck:
-    def __init__(self, names, weights, eps, ppo_slack=1):
+    def __init__(self, names, weights, eps, ppo_slack=1, tie_groups=None):
+        """tie_groups: optional, per brain None or a list of 8 labels -- outputs with one label are EXACT duplicates in the reference (a head
+        whose rows are copies).  The gap that may excuse a differing greedy action is then the one between the two best DISTINCT groups:
+        among duplicates the rule is defined (the first maximum, rl_oracle.c) and a flip inside a group is a failure."""
         from oracle import cpu_bench
         self.names, self.weights, self.eps, self.ppo_slack = names, weights, eps, ppo_slack
+        self.tie_groups = tie_groups
         self.layers = [cpu_bench.unpack(n, w) for n, w in zip(names, weights)]
         self.rows = self.q_rows = 0
         self.max_dq = 0.0
@@ -52,6 +56,14 @@ class PolicyCheck:
                 self.ppo_mismatches += int(bad.sum())
                 assert int(bad.sum()) <= self.ppo_slack, "%s PPO: %d sampled actions differ from the rule on the f32 probabilities" % (what, int(bad.sum()))
             elif bad.any():   # an explored (random) action is the same draw on both sides; a greedy one may flip only inside the tolerance
-                srt = np.sort(ref, axis=1)
-                gap = srt[:, -1] - srt[:, -2]
+                groups = self.tie_groups[b] if self.tie_groups is not None else None
+                if groups is None:
+                    srt = np.sort(ref, axis=1)
+                    gap = srt[:, -1] - srt[:, -2]
+                else:
+                    firsts = sorted({g: i for i, g in reversed(list(enumerate(groups)))}.values())
+                    for i, g in enumerate(groups):
+                        assert np.array_equal(ref[:, i], ref[:, groups.index(g)]), "%s %s: outputs %d and %d are not duplicates in the reference" % (what, name, i, groups.index(g))
+                    srt = np.sort(ref[:, firsts], axis=1)
+                    gap = srt[:, -1] - srt[:, -2] if len(firsts) > 1 else np.full(len(ref), np.inf, np.float32)
                 assert float(gap[bad].max()) < 1e-5, "%s %s: an action differs where the f32 top-2 gap is %.3g" % (what, name, float(gap[bad].max()))

@@ -14,9 +14,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SCRIPT = r'''
-import ctypes, json, sys
+import ctypes, json, os, sys
 import numpy as np
 sys.path.insert(0, %(root)r)
+sys.path.insert(0, os.path.join(%(root)r, "tests"))
 import torch, bench
 from reinlife_amd import _lib
 from reinlife_amd.worlds import DeviceWorlds, pack_brain_weights
@@ -40,7 +41,13 @@ def adversarial(seed):
 
 SHAPES = {"three-brains": dict(n_brains=3, max_agents=150, n_new=140, thr=130, names=["PERD3QN", "D3QN", "PERD3QN"]),
           "crowded-two": dict(n_brains=2, max_agents=200, n_new=190, thr=170, names=["PERD3QN", "PERD3QN"]),
-          "adversarial": dict(n_brains=3, max_agents=150, n_new=140, thr=130, names=["PERD3QN"] * 3)}
+          "adversarial": dict(n_brains=3, max_agents=150, n_new=140, thr=130, names=["PERD3QN"] * 3),
+          "tied": dict(n_brains=3, max_agents=150, n_new=140, thr=130, names=["PERD3QN", "D3QN", "PERD3QN"])}
+
+def tied(name, k):
+    # advantage heads whose eight rows are copies of two or three distinct rows: every row's maximum is an EXACT tie (tests/test_policy_rows_cpu.py)
+    import test_policy_rows_cpu as pr
+    return pr.tied_weights(name, list(pr.TIE_PATTERNS.values())[k], seed=60 + k)
 
 def make(shape, eps):
     sh = SHAPES[shape]
@@ -49,7 +56,7 @@ def make(shape, eps):
     brains = []
     for k, name in enumerate(sh["names"]):
         kind = _lib.KIND_BY_METHOD[name]
-        w = adversarial(100 + k) if shape == "adversarial" else bench.brain_weights(name, 900 + k)
+        w = adversarial(100 + k) if shape == "adversarial" else tied(name, k) if shape == "tied" else bench.brain_weights(name, 900 + k)
         brains.append((kind, eps[k], pack_brain_weights(kind, w, "cuda:0")))
     dw.set_brains(brains)
     dw.reset_synthetic(sh["n_new"])
@@ -100,7 +107,7 @@ def schedule(n_brains, train, t0, n):   # TRAIN 1: a per-tick epsilon schedule (
 def case(shape, train, chunks):
     sh = SHAPES[shape]
     nb, thr, n_new = sh["n_brains"], sh["thr"], sh["n_new"]
-    eps = [0.0] * nb if shape == "adversarial" else [0.2 * (k %% 2) for k in range(nb)]
+    eps = [0.0] * nb if shape in ("adversarial", "tied") else [0.2 * (k %% 2) for k in range(nb)]
     res = dict(shape=shape, train=train, thr=thr, tiles_min=99, tiles_max=0, agents_min=9999, agents_max=0, diff_full=[], diff_loop=[], diff_single=[])
     def note(dw):
         t, n = tiles(dw)
@@ -207,3 +214,19 @@ def test_adversarial_brains_fall_back_on_the_one_wave_tile():
     assert r["diff_full"] == [] and r["diff_loop"] == [] and r["diff_single"] == [], r
     greedy, certified, fell_back = r["counters"]
     assert greedy > 0 and certified == 0 and fell_back > 0, r
+
+
+@pytest.mark.gpu
+def test_exactly_tied_advantages_on_the_one_wave_tile():
+    """Advantage heads whose rows are copies of two or three distinct rows (every row's maximum is an exact tie, all brains greedy) in a
+    six-tile world: whether a row certifies or falls back, the product path, the forced full path, one-tick launches and the two-launch
+    loop choose the same (first) maximum.  The counters are reported, not asserted: a tie between the top two advantages cannot be certified
+    unless the first of them is action 0."""
+    res = _run('("tied", 0, (1, 8, 15)),')
+    assert len(res) == 1
+    r = res[0]
+    _check_tiles(r)
+    assert r["diff_full"] == [] and r["diff_loop"] == [] and r["diff_single"] == [], r
+    greedy, certified, fell_back = r["counters"]
+    print("tied: greedy rows %d, certified %d, fallback tiles %d" % (greedy, certified, fell_back))
+    assert greedy > 0 and r["forced"] == [0, 0, 0], r

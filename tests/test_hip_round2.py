@@ -252,7 +252,8 @@ def test_policy_split_precision_within_row_dynamic_range(capsys):
     operands' low parts bottom out at the f16 subnormal step, 2^-24 of a scaled row maximum in [2^10, 2^11)).  For rows without
     such a spread the second term is far below f32's own rounding; with it, it is what separates the scheme from true f32 --
     an ABSOLUTE error of ~1e-7 * max|x| max|w| on outputs that are themselves that small.  Checked on the input layer (the
-    only one fed arbitrary data) through a DQN whose later layers pass relu(+y), relu(-y) through and recombine them."""
+    only one fed arbitrary DATA; the hidden layers and heads under the same spread of activations and weights:
+    tests/test_hip_policy_rows.py) through a DQN whose later layers pass relu(+y), relu(-y) through and recombine them."""
     import torch
     from reinlife_amd import _lib
     from reinlife_amd.worlds import pack_brain_weights, policy_forward
