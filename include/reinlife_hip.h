@@ -13,6 +13,7 @@
  *                      DQN.py:126-139, D3QN.py:161-173, PERD3QN.py:198-210, PPO.py:101-106,164-169,
  *                      PERDQN.py:101-111,311-323
  *   rl_policy_forward  the bare network forward of one brain on a dense batch of observation rows
+ *   rl_render          Visualize.render()'s drawing of one frame, for any set of worlds     Helpers/render.py:51-239
  *
  * Conventions
  *   - extern "C", plain pointers and sizes; no torch / C++ types.  `stream` is a hipStream_t passed as void*.
@@ -165,7 +166,12 @@ const char* rl_version(void);
 int rl_create(const rl_config* cfg, rl_world** out);
 void rl_destroy(rl_world* h);
 int rl_bind_state(rl_world* h, const rl_state* device_ptrs);
-/* optional device int32[4] that kernels set on inconsistencies: [0] code, [1] world, [2..3] detail */
+/* optional device int32[4] that kernels set on inconsistencies: [0] code, [1] world, [2..3] detail.  The first error stays.  Codes:
+ *   1  a taped _add_food draw (food_k) outside [0, #empty cells)             detail: try, value
+ *   2  a taped birth placement (birth_k) outside [0, #empty cells)           detail: site, value
+ *   3  a world's agent list outgrew slot_cap                                 detail: slots
+ *   4  a taped produce_choice outside [0, RL_N_BEST)                         detail: value
+ *   5  rl_render: a world id outside [0, n_worlds) ([1] = the id)            detail: frame index */
 int rl_bind_error_flag(rl_world* h, int32_t* device_flag);
 
 /* tuning aid: device int64[32] receiving shader-clock stamps at the phase boundaries of world `world` (NULL = off) */
@@ -289,6 +295,29 @@ size_t rl_policy_work_bytes(const rl_world* h);
 int rl_bind_policy_work(rl_world* h, void* work);
 int rl_policy_act(rl_world* h, const rl_brain* brains, int n_brains, const float* obs, int8_t* actions, float* out_q,
                   void* work, void* stream);
+
+/* ---- frames ---------------------------------------------------------------------------------------------------- */
+/* What the painter of Helpers/render.py:51-239 draws, as integers: pixels per cell, the body square (offset, side, border width), the
+ * two eye squares (side, y offset, x offsets) and the food square (offset, side) inside a cell -- computed by the host with the
+ * reference's own expressions; a square whose side is <= 0 is not drawn. */
+typedef struct {
+    int32_t grid_size;                          /* pixels per cell, 1..64 */
+    int32_t body_off, body_size, border;        /* border = 2 (render.py:153) */
+    int32_t eye_size, eye_y, eye_x0, eye_x1;
+    int32_t food_off, food_size;
+    int32_t n_colors;                           /* >= 1 */
+    const double* colors;                       /* device [n_colors][3]: Visualize.colors (a gene's colour is colors[gene mod n_colors]) */
+    const uint8_t* tiles;                       /* device [height][width][3]: every cell's background colour */
+} rl_render_style;
+/* Paints n_frames frames from the bound rl_state (read only) into frames [n_frames][height*gs][width*gs][3] (uint8 RGB, screen x = j,
+ * screen y = i; any alignment), stream-ordered, no host round trip.  Per pixel of cell (i, j), the first that applies: the food square
+ * (cell_type food white, poison black, super food red), an eye (black), the border of the body square (red with RL_F_KILLED, else
+ * body * (1 - health / 205) in float64), the body (colors[gene mod n_colors]), the tile.  Colours are clipped to [0, 255] and
+ * truncated.  The agent of a cell is the LAST entry k < n_agents with RL_F_DEAD clear and (a_i, a_j) = (i, j) on the grid.
+ *   worlds  device int32 [n_frames]: the world of every frame (any order, repeats allowed), or NULL = worlds 0 .. n_frames-1.
+ *           An id outside [0, n_worlds) leaves that frame untouched and sets the bound error flag (code 5).
+ * Nothing but `frames` (and the error flag) is written. */
+int rl_render(rl_world* h, const rl_render_style* style, const int32_t* worlds, int n_frames, uint8_t* frames, void* stream);
 
 /* ---- options -------------------------------------------------------------------------------------------------- */
 /* Tuning / test switches (nothing like them in the reference).  Process-level values start from the environment, read ONCE

@@ -461,6 +461,36 @@ class Environment:
         self.frame = self.viz.frame(self.render_feed(world))
         return True
 
+    def frames(self, worlds=None, out=None):
+        """The frames render() would paint for `worlds` (ids in any order, repeats allowed; None = all worlds), painted on the device by
+        rl_render: a uint8 tensor [n, height*grid_size, width*grid_size, 3] on the environment's device, byte for byte what
+        Visualize.frame gives for each world.  Queued behind the ticks launched so far, without a host round trip; `out` is painted
+        into and returned when given.  (`Helpers.render.mosaic` lays the frames out as one contact sheet.)"""
+        return self.worlds.render(self.viz.style(self.worlds.device), worlds, out)
+
+    def record(self, n_ticks, worlds=(0,), every=1, n_epi=0, out=None):
+        """A film of `worlds` over `n_ticks` ticks of run(): uint8 [1 + n_ticks // every, n, Hpx, Wpx, 3] on the device.  Frame 0 is the
+        state at the call, frame k the state after k * `every` more ticks starting at episode `n_epi`; ticks and painting are queued
+        on one stream with no host wait between them.  Equal to a loop of run(n_epi, every) + frames(worlds)."""
+        if self.rng != "philox":
+            raise ValueError("record() needs rng='philox' (the multi-tick launches of run()); this environment has rng=%r" % self.rng)
+        if every < 1 or n_ticks < 0:
+            raise ValueError("record(): every must be >= 1 and n_ticks >= 0")
+        n_shots = 1 + n_ticks // every
+        n = self.n_worlds if worlds is None else len(worlds)
+        gs = self.viz.grid_size
+        shape = (n_shots, n, self.height * gs, self.width * gs, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.worlds.device)
+        elif tuple(out.shape) != shape:
+            raise ValueError("record(): out must have shape %s" % (shape,))
+        self.frames(worlds, out=out[0])
+        for k in range(1, n_shots):
+            self.run(n_epi, every)
+            n_epi += every
+            self.frames(worlds, out=out[k])
+        return out
+
     def save_results(self, main_folder="experiments"):
         """environment.py:233-256: brains + parameters + results.json + settings.json in the reference's layout."""
         from ..Helpers.saver import SavedAgent, Saver

@@ -59,6 +59,11 @@ class RunOpts(C.Structure):  # rl_run_opts
                 ("trk_skip_ticks", C.c_int32), ("eps_schedule_on_host", C.c_int32), ("replays", C.c_void_p), ("policy_out", C.c_void_p)]
 
 
+class RenderStyle(C.Structure):  # rl_render_style
+    _fields_ = [(n, C.c_int32) for n in ("grid_size", "body_off", "body_size", "border", "eye_size", "eye_y", "eye_x0", "eye_x1",
+                                         "food_off", "food_size", "n_colors")] + [("colors", C.c_void_p), ("tiles", C.c_void_p)]
+
+
 class Brain(C.Structure):
     _fields_ = [("kind", C.c_int32), ("epsilon", C.c_float), ("packed", C.c_void_p)]
 
@@ -94,6 +99,7 @@ ABI = [
     ("rl_policy_work_bytes", C.c_size_t, [_P]),
     ("rl_bind_policy_work", C.c_int, [_P, _P]),
     ("rl_policy_act", C.c_int, [_P, C.POINTER(Brain), C.c_int, _P, _P, _P, _P, _P]),
+    ("rl_render", C.c_int, [_P, C.POINTER(RenderStyle), _P, C.c_int, _P, _P]),
     ("rl_set_option", C.c_int, [C.c_char_p, C.c_char_p]),
     ("rl_get_option", C.c_int, [_P, C.c_char_p]),
     ("rl_philox", None, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

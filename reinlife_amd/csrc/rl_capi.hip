@@ -7,7 +7,7 @@
 
 #include "rl_common.h"
 
-// implemented in rl_world.hip / rl_policy.hip
+// implemented in rl_world.hip / rl_policy.hip / rl_render.hip
 size_t rl_world_smem_bytes(int cpad, int cap, int hash, int plane_stride, int height);
 int rl_world_block();
 int rl_world_launch_step(rl_world*, const int8_t*, const rl_tape*, const rl_step_out*, hipStream_t);
@@ -26,6 +26,7 @@ int rl_policy_pack_impl(int, const float*, float*);
 int rl_policy_forward_impl(int, const float*, const float*, int64_t, float*, hipStream_t);
 size_t rl_policy_work_bytes_impl(const rl_world*);
 int rl_policy_act_impl(rl_world*, const rl_brain*, int, const float*, int8_t*, float*, void*, hipStream_t);
+int rl_render_launch(rl_world*, const rl_render_style*, const int32_t*, int, uint8_t*, hipStream_t);
 
 static thread_local char g_err[512] = "";
 
@@ -386,6 +387,23 @@ int rl_policy_act(rl_world* h, const rl_brain* brains, int n_brains, const float
     for (int b = 0; b < n_brains; ++b)
         if (brains[b].kind < RL_DQN || brains[b].kind > RL_PERDQN || !brains[b].packed) { rl_set_error("rl_policy_act: brain %d invalid", b); return RL_E_INVALID; }
     return rl_policy_act_impl(h, brains, n_brains, obs, actions, out_q, work, (hipStream_t)stream);
+}
+
+int rl_render(rl_world* h, const rl_render_style* style, const int32_t* worlds, int n_frames, uint8_t* frames, void* stream)
+{
+    RL_CHECK_BOUND("rl_render")
+    if (!style) { rl_set_error("rl_render: null style"); return RL_E_INVALID; }
+    if (!frames) { rl_set_error("rl_render: null frames"); return RL_E_INVALID; }
+    if (!style->colors) { rl_set_error("rl_render: style->colors is null"); return RL_E_INVALID; }
+    if (!style->tiles) { rl_set_error("rl_render: style->tiles is null"); return RL_E_INVALID; }
+    if (style->grid_size < 1 || style->grid_size > 64) { rl_set_error("rl_render: style->grid_size must be in [1,64] (got %d)", style->grid_size); return RL_E_INVALID; }
+    if (style->n_colors < 1) { rl_set_error("rl_render: style->n_colors must be >= 1 (got %d)", style->n_colors); return RL_E_INVALID; }
+    if (n_frames < 1) { rl_set_error("rl_render: n_frames must be >= 1 (got %d)", n_frames); return RL_E_INVALID; }
+    if (!worlds && n_frames > h->cfg.n_worlds) {
+        rl_set_error("rl_render: worlds is null (worlds 0..n_frames-1) but n_frames %d > n_worlds %d", n_frames, h->cfg.n_worlds);
+        return RL_E_INVALID;
+    }
+    return rl_render_launch(h, style, worlds, n_frames, frames, (hipStream_t)stream);
 }
 
 void rl_philox(uint64_t seed, uint32_t epoch, uint32_t world, uint32_t tick, uint32_t site, uint32_t index, uint32_t out[4])

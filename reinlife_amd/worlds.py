@@ -324,6 +324,35 @@ class DeviceWorlds:
             d[key] = self.s[key][w].cpu().numpy()
         return d
 
+    def render(self, style, worlds=None, out=None):
+        """Frames of `worlds` (a sequence of world ids in any order, repeats allowed, or a device int32 tensor of them; None = every
+        world) painted on the device from the current state (rl_render): uint8 [n, height*gs, width*gs, 3] on this device.  `style` is
+        Visualize.style(device) (Helpers/render.py).  `out`: a contiguous uint8 tensor of that shape to paint into (it is returned).
+        Queued on torch's current stream behind everything queued so far; nothing is synchronised and the state is not touched."""
+        if worlds is None:
+            ids, n = None, self.R
+        elif torch.is_tensor(worlds) and worlds.is_cuda:   # a caller's device list: its ids are checked by the kernel (error flag)
+            ids = worlds.to(device=self.device, dtype=torch.int32).contiguous().view(-1)
+            n = ids.numel()
+        else:
+            host = np.asarray(worlds.cpu() if torch.is_tensor(worlds) else worlds, dtype=np.int64).reshape(-1)
+            if host.size and (host.min() < 0 or host.max() >= self.R):
+                raise IndexError("render(): world ids must lie in [0, %d), got %s" % (self.R, host[(host < 0) | (host >= self.R)][:4].tolist()))
+            key = host.tobytes()
+            if getattr(self, "_render_ids_key", None) != key:   # (the id list of a loop that paints the same worlds every tick is uploaded once)
+                self._render_ids_key, self._render_ids = key, torch.as_tensor(host.astype(np.int32), device=self.device)
+            ids, n = self._render_ids, host.size
+        if n < 1:
+            raise ValueError("render(): no worlds to paint")
+        gs = int(style.grid_size)
+        shape = (n, self.H * gs, self.W * gs, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif (out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != self._arena.device):
+            raise ValueError("render(): out must be a contiguous uint8 tensor of shape %s on %s" % (shape, self.device))
+        _lib.check(self.lib.rl_render(self.handle, C.byref(style), _ptr(ids), n, _ptr(out), self._stream()), "rl_render")
+        return out
+
     def make_tape(self, tapes):
         """tapes: one dict per world (food_k, food_u, repro_u, birth_k, produce_u, produce_choice) -> device Tape (TapeRing.make): a FRESH
         struct over its own device buffer per call, valid until the fourth make_tape() after it."""
