@@ -14,6 +14,8 @@
  *                      PERDQN.py:101-111,311-323
  *   rl_policy_forward  the bare network forward of one brain on a dense batch of observation rows
  *   rl_render          Visualize.render()'s drawing of one frame, for any set of worlds     Helpers/render.py:51-239
+ *   rl_learn           DQNAgent.train(): the size gate, 5 minibatch updates (smooth-L1, Adam) and the target copy
+ *                      Models/DQN.py:80-83, 142-153 (sampling: :99-113, with replacement here)
  *
  * Conventions
  *   - extern "C", plain pointers and sizes; no torch / C++ types.  `stream` is a hipStream_t passed as void*.
@@ -60,7 +62,7 @@ enum { RL_F_DEAD = 1, RL_F_REPRODUCED = 2, RL_F_KILLED = 4, RL_F_ATE_SUPER = 8, 
 enum { RL_DQN = 0, RL_D3QN = 1, RL_PERD3QN = 2, RL_PPO = 3, RL_PERDQN = 4 };
 /* Philox draw sites */
 enum { RL_SITE_FOOD = 1, RL_SITE_REPRO = 2, RL_SITE_BIRTH = 3, RL_SITE_PRODUCE = 4, RL_SITE_ACT = 5,
-       RL_SITE_RESET_AGENT = 6, RL_SITE_RESET_FOOD = 7, RL_SITE_RESET_POISON = 8, RL_SITE_RESET_SUPER = 9 };
+       RL_SITE_RESET_AGENT = 6, RL_SITE_RESET_FOOD = 7, RL_SITE_RESET_POISON = 8, RL_SITE_RESET_SUPER = 9, RL_SITE_LEARN = 10 };
 
 /* keyword arguments of Environment(...) that matter on the path (environment.py:74-89) */
 typedef struct {
@@ -171,7 +173,8 @@ int rl_bind_state(rl_world* h, const rl_state* device_ptrs);
  *   2  a taped birth placement (birth_k) outside [0, #empty cells)           detail: site, value
  *   3  a world's agent list outgrew slot_cap                                 detail: slots
  *   4  a taped produce_choice outside [0, RL_N_BEST)                         detail: value
- *   5  rl_render: a world id outside [0, n_worlds) ([1] = the id)            detail: frame index */
+ *   5  rl_render: a world id outside [0, n_worlds) ([1] = the id)            detail: frame index
+ *   6  rl_learn: a minibatch slot outside [0, ring size) ([1] = brain index) detail: step, value */
 int rl_bind_error_flag(rl_world* h, int32_t* device_flag);
 
 /* tuning aid: device int64[32] receiving shader-clock stamps at the phase boundaries of world `world` (NULL = off) */
@@ -295,6 +298,57 @@ size_t rl_policy_work_bytes(const rl_world* h);
 int rl_bind_policy_work(rl_world* h, void* work);
 int rl_policy_act(rl_world* h, const rl_brain* brains, int n_brains, const float* obs, int8_t* actions, float* out_q,
                   void* work, void* stream);
+
+/* ---- learning -------------------------------------------------------------------------------------------------- */
+/* One learning brain of an rl_learn call: what DQNAgent owns besides its replay memory (Models/DQN.py:48-55 -- agent, target, optimizer)
+ * as caller-owned device buffers, all in state-dict-flat order (rl_policy_pack_weights), plus the hyperparameters of DQN.py:14-16, 52. */
+typedef struct {
+    int32_t kind;                 /* RL_DQN; anything else: RL_E_UNSUPPORTED naming the kind */
+    float *params, *target;       /* device [rl_policy_n_params(kind)], state-dict order */
+    float *adam_m, *adam_v;       /* device, same size, zeroed once by the caller */
+    int64_t* state;               /* device [2]: Adam steps taken, rl_learn calls made */
+    float* packed;                /* device [rl_policy_packed_floats(kind)]: rewritten at the end of every call */
+    float lr, gamma, beta1, beta2, eps;
+    int32_t batch, min_size, sync_target;
+    float* loss;                  /* device [n_steps] or NULL */
+    float* grad;                  /* device [n_steps][n_params] or NULL (tests, diagnostics) */
+} rl_learner;
+/* 1 for the brain kinds rl_learn trains (RL_DQN), 0 for the others */
+int rl_learn_supported(int kind);
+/* DQNAgent.train() (DQN.py:80-83 -> train(), :142-153) for n_learners brains in ONE stream-ordered launch, one workgroup per brain:
+ * learner i trains on rings[i] (n_learners <= RL_MAX_CAPTURE_BRAINS; both are host arrays, copied during the call).
+ *   size gate   size = min(*ring.count, ring.capacity), read on the device; size <= min_size: no update (DQN.py:81)
+ *   n_steps     sequential minibatch updates (the reference: 5), each: batch rows (1..32) of the ring -> q = Q_eval(state),
+ *               target = reward + gamma * max_a Q_target(state_prime) * (1 - done), loss = mean smooth_l1(q[action] - target) (beta 1),
+ *               its gradient through the network, and torch.optim.Adam's update (no weight decay, no amsgrad; bias corrections in
+ *               double from the step count state[0]; lr, beta1, beta2 are re-read as the decimal that "%.7g" prints for them --
+ *               0.999f means 0.999, as torch's Python floats do; a float that is NOT a decimal of at most 7 digits is rounded to one)
+ *               of params / adam_m / adam_v.  loss[s] and grad[s][n_params] are written when given.
+ *   rows        slots != NULL: device int32 [n_learners][n_steps][batch] ring slots, duplicates allowed (they count twice).  A slot
+ *               outside [0, size) of a ring above the size gate sets error-flag code 6 and that brain leaves the call with NONE of its buffers touched (the others
+ *               train).  slots == NULL: slot = ((uint64)x * size) >> 32, x = word 0 of rl_philox(seed, 0, i, (uint32)state[1],
+ *               RL_SITE_LEARN, s * batch + j): uniform WITH replacement -- the reference's random.sample (DQN.py:100) draws without.
+ *   afterwards  sync_target != 0: target <- params (DQN.py:83, also below the size gate); state[0] += updates made; state[1] += 1;
+ *               `packed` is rewritten from the final params, bit for bit what rl_policy_pack_weights makes of them -- the acting
+ *               kernels that hold this pointer (rl_brain.packed) act on the new weights from the next launch of the stream on.
+ * Deterministic: the same buffers give the same bits in every run and whatever else is in the launch.  The handle supplies the Philox
+ * seed and the error flag; it need not be bound. */
+int rl_learn(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, const int32_t* slots,
+             void* stream);
+
+/* The `slots` of an rl_learn call drawn so that they do not depend on the ORDER of a ring's rows: rl_run_ex / rl_capture_transitions
+ * append every world's transitions with an atomic add on the ring's counter, so two identical runs hold the same transitions in other
+ * slots, and rl_learn's own draw (slots == NULL), which names slots, would train them differently.  Here every row gets a 64-bit key of
+ * its content (state, state_prime, action, reward, done, age) and draw d = s * batch + j takes the row whose key, mixed with words 0-1 of
+ * rl_philox(seed, 0, i, (uint32)state[1], RL_SITE_LEARN, d), is smallest: empirically uniform over the rows (as good as the mixing function), WITH replacement, the same rows
+ * whatever slots they sit in (equal rows are interchangeable; distinct rows with equal keys: 2^-64).
+ *   keys    host array [n_learners] of device uint64 [ring capacity] scratch, rewritten by every call
+ *   slots   device int32, the learners' [n_steps][batch] tables laid end to end (what rl_learn takes when all batches are equal)
+ * Two launches (keys of the rows a ring holds, then one workgroup per draw); call it in front of rl_learn on the same stream.  What it
+ * cannot mend: a launch that appends MORE than a ring's capacity overwrites its own rows in append order -- which rows survive then
+ * differs from run to run. */
+int rl_learn_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps,
+                  unsigned long long* const* keys, int32_t* slots, void* stream);
 
 /* ---- frames ---------------------------------------------------------------------------------------------------- */
 /* What the painter of Helpers/render.py:51-239 draws, as integers: pixels per cell, the body square (offset, side, border width), the

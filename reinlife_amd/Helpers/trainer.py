@@ -4,9 +4,10 @@ The loop is the reference's (get_action -> step -> learn -> update_env, trainer.
 GPU through env.act().  A single world (rng="reference", the default for n_worlds == 1 outside a multi-rank job) makes every random draw of the
 loop exactly as the reference does, so the same seeds give the same run; replicated worlds draw in-kernel.
 
-INFERENCE ONLY: training=True (the reference's default) keeps the loop, the epsilon schedules and the Tracker, but the brains
-of this build do not learn -- Environment warns about it, and save=True writes the weights as they were loaded / initialised
-(settings.json says so).  Training is outside this build's scope (BASELINE.json north_star)."""
+By default (learn=None) the run is INFERENCE ONLY: training=True (the reference's default) keeps the loop, the epsilon schedules and
+the Tracker, but the brains do not learn -- Environment warns about it, and save=True writes the weights as they were loaded /
+initialised (settings.json says so).  learn="device" trains the DQN brains on the GPU (rl_learn); see trainer()'s docstring for how
+its schedule and sampling differ from the reference's."""
 import time
 
 import torch
@@ -17,7 +18,8 @@ from ..World.environment import Environment
 def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=False, google_colab=False, update_interval=500,
             print_results=True, max_agents=100, render=False, static_families=True, training=True, save=True,
             limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None, seed=0, rng=None, per_agent_api=False,
-            fused=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None):
+            fused=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
+            learn_steps=5):
     """Extra keyword-only arguments: n_worlds / device / seed / rng / synthetic_agents / refill_below (Environment); per_agent_api=True makes the reference's literal
     per-agent get_action / learn calls; fused (default: True for rng="philox" without per_agent_api) runs the loop through
     Environment.run -- whole chunks of ticks per launch, ending where the Tracker closes an interval -- instead of three launches
@@ -27,13 +29,29 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     call -- or pass the process-group module as `dist`.  Every rank then owns `n_worlds` replicas (global ids rank * n_worlds ...: the
     worlds are the same whatever the number of ranks), runs on cuda:LOCAL_RANK unless `device` says otherwise, and the Tracker's
     per-interval statistics (tracker.py:107-121) are pooled over ALL ranks' worlds by one all-gather of the ranks' per-world sums per closed interval --
-    the only collective of the loop; every rank returns the same `env.tracker.results`."""
+    the only collective of the loop; every rank returns the same `env.tracker.results`.
+    learn="device" (default None: nothing learns, as before): every DQN brain of `brains` trains on the GPU.  The multi-tick launches
+    append each tick's transitions to per-brain replay rings of 50,000 (DQN.py:15); after every episode that is a multiple of
+    `learn_every` (default: the brains' train_freq, 20) three launches follow the chunk -- two that draw the minibatches (rl_learn_draw) and
+    ONE rl_learn that makes `learn_steps` (default 5, DQN.py:143) minibatch updates per brain -- batch 32, gamma 0.98, smooth-L1, Adam, only once a ring holds more than 1000 transitions -- copies agent ->
+    target (DQN.py:83) and rewrites the packed weights the worlds act with, all on the same stream with no host round trip; after the
+    loop the trained parameters are copied into the brains' modules, so save=True writes them.  Brains of other kinds stay frozen (a
+    warning names them).  Needs rng="philox", the fused path, static_families=True, training=True and a single rank (ValueError
+    otherwise).  TWO DEVIATIONS from the reference: (1) the schedule -- the reference calls train() per agent whenever its age is a
+    multiple of train_freq or it died (DQN.py:85-89: over a thousand dependent train() calls per tick at 256 worlds); here a brain
+    trains once per `learn_every` ticks of world time, as a single long-lived agent would cause; (2) minibatches are drawn uniformly
+    WITH replacement, where the reference's random.sample (DQN.py:100) draws without -- and by a key of the rows' content mixed with
+    Philox bits rather than by slot, because the worlds append to a ring in a timing-dependent order: a second identical call gives the
+    same parameters bit for bit unless one chunk appends more than a ring holds."""
+    if learn == "device" and (per_agent_api or fused is False):
+        raise ValueError("trainer(learn='device') needs the fused path (fused=True, per_agent_api=False): the replay rings are filled "
+                         "inside the multi-tick launches")
     env = Environment(width=width, height=height, max_agents=max_agents, brains=brains, grid_size=24,
                       static_families=static_families, update_interval=update_interval, print_results=print_results,
                       interactive_results=visualize_results, google_colab=google_colab, training=training,
                       limit_reproduction=limit_reproduction, incentivize_killing=incentivize_killing, n_worlds=n_worlds,
                       device=device, seed=seed, rng=rng, synthetic_agents=synthetic_agents, refill_below=refill_below, dist=dist,
-                      world_base=world_base)
+                      world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps)
     env.reset()
     if fused is None:
         fused = env.rng == "philox" and not per_agent_api
@@ -66,6 +84,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     torch.cuda.synchronize(env.worlds.device)      # the loop is over when the device is
     env.loop_seconds = time.perf_counter() - t0
     env.worlds.check_error_flag()                  # (a read-back of its own: after the clock)
+    env.sync_learners()                            # learn="device": the trained parameters into the brains' modules
     if save:
         env.save_results()
     return env

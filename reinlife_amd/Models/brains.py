@@ -3,8 +3,9 @@
 reference's `pretrained/*.pt` files.  The forward pass and action selection run in libreinlife_hip.so (f32-grade block-scaled f16 MFMA):
 batched over all agents through Environment.act(), or one state at a time through get_action().
 
-Training (replay buffers, optimizers, learn()) is outside this build's scope (BASELINE.json north_star): learn() is
-accepted and ignored so that trainer() loops written for the reference keep running; a warning is issued once.
+The per-agent learn() of the reference's brains is accepted and ignored, so that trainer() loops written for the reference keep
+running (a warning is issued once).  DQN brains learn on the device instead, through trainer(learn="device") / learn.DeviceLearner
+(rl_learn); the other kinds stay frozen.
 """
 import random
 import warnings
@@ -110,6 +111,7 @@ class DQNAgent(_HipBrain):
         self.max_epi = max_epi
         self.epsilon = 0.20
         self.train_freq = train_freq
+        self.learning_rate = learning_rate   # (read by learn.DeviceLearner; the reference hands it to its optimizer, DQN.py:52)
         self.training = training
         if not self.training:
             self.epsilon = 0

@@ -157,9 +157,12 @@ class Environment:
     def __init__(self, width=30, height=30, brains=None, grid_size=16, max_agents=50, update_interval=500, print_results=True,
                  static_families=True, interactive_results=False, google_colab=False, training=True, save=False,
                  pastel_colors=False, limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None,
-                 seed=0, rng=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None):
+                 seed=0, rng=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
+                 learn_steps=5):
         if not brains:
             raise ValueError("Environment needs a non-empty list of brains")
+        if learn not in (None, "device"):
+            raise ValueError("learn must be None (the brains stay as they are) or 'device' (DQN brains train through rl_learn), got %r" % (learn,))
         self.width, self.height = width, height
         self.actions, self.entities = Actions, EntityTypes
         self.brains = brains
@@ -201,6 +204,20 @@ class Environment:
             raise ValueError("synthetic_agents / refill_below need rng='philox'")
         if refill_below is not None and synthetic_agents is None:
             raise ValueError("refill_below needs synthetic_agents (the population a re-generated world starts with)")
+        self.learn, self.learn_steps, self.learners = learn, int(learn_steps), {}
+        if learn == "device":   # every condition is checked before a device is touched
+            if self.rng != "philox":
+                raise ValueError("learn='device' needs rng='philox' (the multi-tick launches that fill the replay rings); this environment has rng=%r" % self.rng)
+            if not static_families:
+                raise ValueError("learn='device' needs static_families=True: per-gene brain copies (non-static families) do not learn yet")
+            if not training:
+                raise ValueError("learn='device' needs training=True")
+            if self.world_size > 1:
+                raise ValueError("learn='device' runs on a single rank: multi-rank training needs a weight collective (world size %d)" % self.world_size)
+            if len(brains) > _lib.MAX_CAPTURE_BRAINS:
+                raise ValueError("learn='device' captures transitions for at most %d brains (got %d)" % (_lib.MAX_CAPTURE_BRAINS, len(brains)))
+            if self.learn_steps < 1 or (learn_every is not None and int(learn_every) < 1):
+                raise ValueError("learn_steps and learn_every must be >= 1")
         self.best_agents = []
         # environment.py:118: the painter is built first (pastel colours draw from `random` here, its background tiles at
         # the first render() -- both matter for same-seed runs)
@@ -226,7 +243,23 @@ class Environment:
         self._brains_bound, self._bound_key = False, None
         self._ticks_since_check = 0
         self.loop_seconds = None    # wall time of the last trainer() / tester() loop on this environment (set by them)
-        if training:
+        self.learn_every = None
+        if learn == "device":
+            # the replay rings of DQN.py:15 (buffer_limit), filled inside the multi-tick launches; one learner per brain rl_learn trains,
+            # whose packed tensor IS that brain's acting weights from here on (rl_learn rewrites it in place)
+            from ..learn import BUFFER_LIMIT, DeviceLearner
+            self.worlds.enable_capture(BUFFER_LIMIT)
+            lib = _lib.lib()
+            for k, b in enumerate(brains):
+                if lib.rl_learn_supported(b.kind):
+                    self.learners[k] = DeviceLearner(b, self.worlds.device, ring=self.worlds.replays[k])
+            if not self.learners:
+                raise ValueError("learn='device': none of the brains is of a kind rl_learn trains (DQN)")
+            self.learn_every = int(learn_every) if learn_every is not None else min(l.train_freq for l in self.learners.values())
+            frozen = ["%d (%s)" % (k, b.method) for k, b in enumerate(brains) if k not in self.learners]
+            if frozen:
+                warn_inference_only(frozen)
+        elif training:
             warn_inference_only()
 
     # -- the host view of the device state: materialised on first read after every state change ------------------------------
@@ -263,7 +296,7 @@ class Environment:
     def _bind_brains(self):
         """The brains' packed weights and current exploration rates on the device.  Weights are packed and uploaded when they have
         changed (packed_weights() keys its cache on the parameters' storage and version counters); otherwise only the rates move."""
-        packed = [b.packed_weights(self.device) for b in self.brains]
+        packed = [self.learners[k].packed if k in self.learners else b.packed_weights(self.device) for k, b in enumerate(self.brains)]
         key = tuple((b.kind, id(p)) for b, p in zip(self.brains, packed))   # (a repack makes a new tensor object)
         eps = [float(getattr(b, "epsilon", 0.0)) for b in self.brains]
         if self._brains_bound and key == self._bound_key:
@@ -496,14 +529,34 @@ class Environment:
         from ..Helpers.saver import SavedAgent, Saver
         settings = {"Update interval": self.tracker.update_interval, "Width": self.width, "Height": self.height,
                     "Max agents": self.max_agents, "Families": self.static_families,
-                    # (extra key, not in the reference's file) this build never updates weights: say so next to them
-                    "Weights": "as loaded / initialised -- reinlife_amd runs inference only, learn() is a no-op"}
+                    # (extra key, not in the reference's file) which weights were updated: say so next to them
+                    "Weights": self._weights_note()}
         if self.static_families:
             agents = [SavedAgent(g, b) for g, b in enumerate(self.brains)]
         else:  # the brains the best agents descend from (inference-time copies share their weights)
             bb = self.worlds.s["best_brain"][0].cpu().numpy()
             agents = [SavedAgent(int(self.max_gene), self.brains[int(b)]) for b in bb]
         return Saver(main_folder, google_colab=self.google_colab).save(agents, self.static_families, self.tracker.results, settings)
+
+    def _weights_note(self):
+        if not self.learners:
+            return "as loaded / initialised -- reinlife_amd runs inference only, learn() is a no-op"
+        frozen = [k for k in range(len(self.brains)) if k not in self.learners]
+        return ("brains %s trained on the device (rl_learn: %d minibatch updates every %d episodes, rows drawn by content key with replacement)"
+                % (sorted(self.learners), self.learn_steps, self.learn_every)
+                + ("; brains %s as loaded / initialised (their kinds do not learn in this build)" % frozen if frozen else ""))
+
+    def learn_now(self):
+        """One DQNAgent.train() (DQN.py:80-83) for every learner, queued behind the ticks launched so far (DeviceWorlds.learn).  The
+        minibatches are drawn by the rows' content (DeviceWorlds.draw_slots): the rings' order differs from run to run, the run does not."""
+        if self.learners:
+            ls = [self.learners[k] for k in sorted(self.learners)]
+            self.worlds.learn(ls, self.learn_steps, slots=self.worlds.draw_slots(ls, self.learn_steps))
+
+    def sync_learners(self):
+        """The trained parameters into the brains' modules (DeviceLearner.sync_to_module): what Saver and state_dict() read."""
+        for l in self.learners.values():
+            l.sync_to_module()
 
     # -- fused loop ----------------------------------------------------------------------------------------------------
     def run(self, n_epi=0, n_ticks=1, max_chunk=4096):
@@ -512,7 +565,9 @@ class Environment:
         (rl_run_ex: worlds resident in LDS, the brains' per-episode epsilon as a schedule, the Tracker's statistics accumulated in the
         launch); chunks end where the reference's Tracker closes an interval (n_epi % update_interval == 0, tracker.py:107-121); episode
         0's statistics never reach an aggregate (tracker.py:279-282) and are left out inside the launch.  Same results as calling
-        act() / step() / update_env() tick by tick (tests/test_hip_round3.py)."""
+        act() / step() / update_env() tick by tick (tests/test_hip_round3.py).
+        learn="device": chunks also end at the episodes that are multiples of learn_every, and behind each such chunk the minibatch draw (two launches)
+        and ONE rl_learn for all learners are queued on the same stream (learn_now) -- this build's schedule, not the reference's per-agent one."""
         if self.rng != "philox":
             for t in range(n_ticks):
                 self.act(n_epi + t); self.step(); self.update_env(n_epi + t)
@@ -523,6 +578,8 @@ class Environment:
             k = min(n_ticks, max_chunk)
             if self.training and n_epi + k - 1 >= interval:   # up to and including the next episode that closes a Tracker interval
                 k = min(k, (max(n_epi, 1) + interval - 1) // interval * interval - n_epi + 1)
+            if self.learners:   # ... and the next episode after which the brains train
+                k = min(k, (max(n_epi, 1) + self.learn_every - 1) // self.learn_every * self.learn_every - n_epi + 1)
             eps = self._epsilon_schedule(n_epi, k)
             self._bind_brains()   # (the brains' current epsilon = the last row; weights are uploaded only when they changed)
             if self.training and n_epi == 0:
@@ -536,6 +593,8 @@ class Environment:
             self.tracker.resolve()
             self._refresh(after="update")
             last = n_epi + k - 1
+            if self.learners and last > 0 and last % self.learn_every == 0:
+                self.learn_now()
             if self.training and last > 0 and last % interval == 0:
                 self.tracker.update_results(None, last, defer=True)   # the device half of the close: queued behind the chunk
             n_epi += k
@@ -636,8 +695,12 @@ def resolve_dist(dist=None):
     return None, 0, 1
 
 
-def warn_inference_only():
+def warn_inference_only(frozen=None):
     import warnings
+    if frozen is not None:
+        warnings.warn("learn='device' trains the DQN brains of this run; brains %s are of kinds rl_learn does not train yet: they stay "
+                      "inference only -- brain.learn() is a no-op for them and their weights are NOT updated." % ", ".join(frozen), stacklevel=3)
+        return
     warnings.warn("reinlife_amd runs ReinLife's per-tick path (world tick + policy inference) only: training=True keeps the "
                   "reference's loop, epsilon schedules and Tracker, but brain.learn() is a no-op and the brains' weights are NOT "
                   "updated; results saved from such a run hold the initial (untrained) weights.  Train with the reference, or feed "

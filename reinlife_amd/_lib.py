@@ -64,6 +64,16 @@ class RenderStyle(C.Structure):  # rl_render_style
                                          "food_off", "food_size", "n_colors")] + [("colors", C.c_void_p), ("tiles", C.c_void_p)]
 
 
+class Learner(C.Structure):  # rl_learner
+    _fields_ = ([("kind", C.c_int32)] + [(n, C.c_void_p) for n in ("params", "target", "adam_m", "adam_v", "state", "packed")]
+                + [(n, C.c_float) for n in ("lr", "gamma", "beta1", "beta2", "eps")]
+                + [(n, C.c_int32) for n in ("batch", "min_size", "sync_target")] + [("loss", C.c_void_p), ("grad", C.c_void_p)])
+
+
+SITE_LEARN = 10          # RL_SITE_LEARN: the Philox site of rl_learn's minibatch draws
+MAX_CAPTURE_BRAINS = 16  # RL_MAX_CAPTURE_BRAINS
+
+
 class Brain(C.Structure):
     _fields_ = [("kind", C.c_int32), ("epsilon", C.c_float), ("packed", C.c_void_p)]
 
@@ -99,6 +109,9 @@ ABI = [
     ("rl_policy_work_bytes", C.c_size_t, [_P]),
     ("rl_bind_policy_work", C.c_int, [_P, _P]),
     ("rl_policy_act", C.c_int, [_P, C.POINTER(Brain), C.c_int, _P, _P, _P, _P, _P]),
+    ("rl_learn_supported", C.c_int, [C.c_int]),
+    ("rl_learn", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, C.POINTER(_P), _P, _P]),
     ("rl_render", C.c_int, [_P, C.POINTER(RenderStyle), _P, C.c_int, _P, _P]),
     ("rl_set_option", C.c_int, [C.c_char_p, C.c_char_p]),
     ("rl_get_option", C.c_int, [_P, C.c_char_p]),

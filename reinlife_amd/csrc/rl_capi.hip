@@ -7,7 +7,7 @@
 
 #include "rl_common.h"
 
-// implemented in rl_world.hip / rl_policy.hip / rl_render.hip
+// implemented in rl_world.hip / rl_policy.hip / rl_render.hip / rl_learn.hip
 size_t rl_world_smem_bytes(int cpad, int cap, int hash, int plane_stride, int height);
 int rl_world_block();
 int rl_world_launch_step(rl_world*, const int8_t*, const rl_tape*, const rl_step_out*, hipStream_t);
@@ -27,6 +27,9 @@ int rl_policy_forward_impl(int, const float*, const float*, int64_t, float*, hip
 size_t rl_policy_work_bytes_impl(const rl_world*);
 int rl_policy_act_impl(rl_world*, const rl_brain*, int, const float*, int8_t*, float*, void*, hipStream_t);
 int rl_render_launch(rl_world*, const rl_render_style*, const int32_t*, int, uint8_t*, hipStream_t);
+int rl_learn_supported_impl(int);
+int rl_learn_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, const int32_t*, hipStream_t);
+int rl_learn_draw_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, unsigned long long* const*, int32_t*, hipStream_t);
 
 static thread_local char g_err[512] = "";
 
@@ -387,6 +390,43 @@ int rl_policy_act(rl_world* h, const rl_brain* brains, int n_brains, const float
     for (int b = 0; b < n_brains; ++b)
         if (brains[b].kind < RL_DQN || brains[b].kind > RL_PERDQN || !brains[b].packed) { rl_set_error("rl_policy_act: brain %d invalid", b); return RL_E_INVALID; }
     return rl_policy_act_impl(h, brains, n_brains, obs, actions, out_q, work, (hipStream_t)stream);
+}
+
+int rl_learn_supported(int kind) { return rl_learn_supported_impl(kind); }
+
+int rl_learn(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, const int32_t* slots, void* stream)
+{
+    if (!h) { rl_set_error("rl_learn: null handle"); return RL_E_INVALID; }
+    if (!learners || !rings) { rl_set_error("rl_learn: null learners / rings"); return RL_E_INVALID; }
+    if (n_learners < 1 || n_learners > RL_MAX_CAPTURE_BRAINS) { rl_set_error("rl_learn: n_learners must be in [1,%d] (got %d)", RL_MAX_CAPTURE_BRAINS, n_learners); return RL_E_INVALID; }
+    if (n_steps < 1) { rl_set_error("rl_learn: n_steps must be >= 1 (got %d)", n_steps); return RL_E_INVALID; }
+    for (int i = 0; i < n_learners; ++i) {
+        const rl_learner& l = learners[i];
+        const rl_replay& r = rings[i];
+        if (!rl_learn_supported_impl(l.kind)) { rl_set_error("rl_learn: learner %d has brain kind %d; this library trains RL_DQN (0) only (rl_learn_supported)", i, l.kind); return RL_E_UNSUPPORTED; }
+        if (!l.params || !l.target || !l.adam_m || !l.adam_v || !l.state || !l.packed) { rl_set_error("rl_learn: learner %d: params / target / adam_m / adam_v / state / packed must not be null", i); return RL_E_INVALID; }
+        if (l.batch < 1 || l.batch > 32) { rl_set_error("rl_learn: learner %d: batch must be in [1,32] (got %d)", i, l.batch); return RL_E_INVALID; }
+        if (!r.state || !r.state_prime || !r.action || !r.reward || !r.done || !r.count || r.capacity < 1 || r.capacity > 0x7fffffff) { rl_set_error("rl_learn: replay %d incomplete (state / state_prime / action / reward / done / count, capacity in [1, 2^31))", i); return RL_E_INVALID; }
+    }
+    DeviceGuard guard(device_of_pointer(learners[0].params));
+    return rl_learn_launch(h, learners, rings, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+int rl_learn_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, unsigned long long* const* keys,
+                  int32_t* slots, void* stream)
+{
+    if (!h) { rl_set_error("rl_learn_draw: null handle"); return RL_E_INVALID; }
+    if (!learners || !rings || !keys || !slots) { rl_set_error("rl_learn_draw: null learners / rings / keys / slots"); return RL_E_INVALID; }
+    if (n_learners < 1 || n_learners > RL_MAX_CAPTURE_BRAINS) { rl_set_error("rl_learn_draw: n_learners must be in [1,%d] (got %d)", RL_MAX_CAPTURE_BRAINS, n_learners); return RL_E_INVALID; }
+    if (n_steps < 1) { rl_set_error("rl_learn_draw: n_steps must be >= 1 (got %d)", n_steps); return RL_E_INVALID; }
+    for (int i = 0; i < n_learners; ++i) {
+        const rl_replay& r = rings[i];
+        if (!learners[i].state || !keys[i]) { rl_set_error("rl_learn_draw: learner %d: state / keys must not be null", i); return RL_E_INVALID; }
+        if (learners[i].batch < 1 || learners[i].batch > 32) { rl_set_error("rl_learn_draw: learner %d: batch must be in [1,32] (got %d)", i, learners[i].batch); return RL_E_INVALID; }
+        if (!r.state || !r.state_prime || !r.action || !r.reward || !r.done || !r.age || !r.count || r.capacity < 1 || r.capacity > 0x7fffffff) { rl_set_error("rl_learn_draw: replay %d incomplete (state / state_prime / action / reward / done / age / count, capacity in [1, 2^31))", i); return RL_E_INVALID; }
+    }
+    DeviceGuard guard(device_of_pointer(slots));
+    return rl_learn_draw_launch(h, learners, rings, n_learners, n_steps, keys, slots, (hipStream_t)stream);
 }
 
 int rl_render(rl_world* h, const rl_render_style* style, const int32_t* worlds, int n_frames, uint8_t* frames, void* stream)

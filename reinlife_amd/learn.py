@@ -1,0 +1,91 @@
+"""DeviceLearner: what a DQN brain needs to learn on the device (rl_learn, include/reinlife_hip.h) -- the flat f32 master parameters,
+the target network, Adam's moments, the step / call counters and the packed weights the acting kernels read, all as device tensors.
+
+Reference: DQNAgent owns `agent`, `target`, `memory` and `optimizer` (ReinLife/Models/DQN.py:48-52); train() (DQN.py:80-83, 142-153)
+samples 5 minibatches of 32 and makes one Adam step on each, then copies agent -> target.  Here the replay memory is the brain's
+rl_replay ring (DeviceWorlds.enable_capture) and the five steps are ONE launch (DeviceWorlds.learn).  Two deviations, stated wherever
+this is documented: minibatches are drawn WITH replacement (the reference's random.sample draws without), and the schedule of train()
+calls is the caller's (Environment: once per `learn_every` episodes), not "whenever an agent's age is a multiple of train_freq"."""
+import copy
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+GAMMA, BATCH, MIN_SIZE, BUFFER_LIMIT = 0.98, 32, 1000, 50_000   # DQN.py:14-16, 81
+
+
+class DeviceLearner:
+    def __init__(self, brain, device="cuda:0", ring=None):
+        lib = _lib.lib()
+        if not lib.rl_learn_supported(brain.kind):
+            raise ValueError("rl_learn does not train %s brains (kind %d): only DQN learns on the device" % (brain.method, brain.kind))
+        from .worlds import pack_brain_weights
+        self.brain, self.kind, self.device = brain, brain.kind, torch.device(device)
+        flat = brain.state_dict_flat()
+        self.n_params = int(lib.rl_policy_n_params(self.kind))
+        self.params = torch.as_tensor(flat, device=self.device)
+        self.target = self.params.clone()                       # DQN.py:50
+        self.adam_m = torch.zeros_like(self.params)
+        self.adam_v = torch.zeros_like(self.params)
+        self.state = torch.zeros(2, dtype=torch.int64, device=self.device)   # [Adam steps taken, rl_learn calls made]
+        self.packed = pack_brain_weights(self.kind, flat, self.device)
+        self.lr = float(getattr(brain, "learning_rate", 0.0005))
+        self.train_freq = int(getattr(brain, "train_freq", 20))
+        self.gamma, self.batch, self.min_size = GAMMA, BATCH, MIN_SIZE
+        self.beta1, self.beta2, self.eps = 0.9, 0.999, 1e-8      # torch.optim.Adam's defaults (DQN.py:52)
+        self.sync_target = True                                  # DQN.py:83
+        self.ring = ring          # the brain's replay ring: a dict of device tensors as DeviceWorlds.enable_capture() makes them
+        self.loss = None          # optional device float32 [n_steps]
+        self.grad = None          # optional device float32 [n_steps, n_params] (tests, diagnostics)
+
+    def struct(self):
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        return _lib.Learner(self.kind, p(self.params), p(self.target), p(self.adam_m), p(self.adam_v), p(self.state), p(self.packed),
+                            self.lr, self.gamma, self.beta1, self.beta2, self.eps, self.batch, self.min_size, int(self.sync_target),
+                            p(self.loss), p(self.grad))
+
+    def ring_struct(self):
+        r = self.ring
+        if r is None:
+            raise _lib.ReinLifeHipError("this DeviceLearner has no replay ring (DeviceLearner.ring)")
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        return _lib.Replay(*[p(r.get(n)) for n in ("state", "state_prime", "action", "reward", "done", "prob", "age", "count")],
+                           int(r["state"].shape[0]))
+
+    @property
+    def steps(self):
+        """Adam steps taken so far (reads the device counter: synchronises)."""
+        return int(self.state[0].item())
+
+    def _load(self, module, flat):
+        off = 0
+        with torch.no_grad():
+            for t in module.state_dict().values():
+                n = t.numel()
+                t.copy_(torch.from_numpy(flat[off:off + n].reshape(tuple(t.shape))))
+                off += n
+        assert off == flat.size
+
+    def sync_to_module(self):
+        """The trained parameters into brain.agent and the target network's into brain.target (made on first use: a copy, no
+        generator draw), so that Saver and state_dict() see them."""
+        self._load(self.brain.agent, self.params.cpu().numpy())
+        if getattr(self.brain, "target", None) is None:
+            self.brain.target = copy.deepcopy(self.brain.agent)
+        self._load(self.brain.target, self.target.cpu().numpy())
+
+
+def philox_slots(seed, brain_index, calls, n_steps, batch, size):
+    """The ring slots rl_learn draws when it is given none: word 0 of rl_philox(seed, 0, brain_index, calls, RL_SITE_LEARN, s * batch + j)
+    mapped to [0, size) by ((uint64)x * size) >> 32 -> int32 [n_steps, batch]."""
+    lib = _lib.lib()
+    out = (C.c_uint32 * 4)()
+    slots = np.zeros((n_steps, batch), np.int32)
+    for s in range(n_steps):
+        for j in range(batch):
+            lib.rl_philox(seed, 0, brain_index, calls & 0xffffffff, _lib.SITE_LEARN, s * batch + j, C.byref(out))
+            slots[s, j] = (int(out[0]) * int(size)) >> 32
+    return slots

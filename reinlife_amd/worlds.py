@@ -414,6 +414,49 @@ class DeviceWorlds:
                                                    C.byref(self._step_out), self._replay_arr, self.n_brains, self._stream()),
                    "rl_capture_transitions")
 
+    def draw_slots(self, learners, n_steps):
+        """Ring slots for learn(learners, n_steps, slots=...) that do not depend on the ORDER of the rings' rows (rl_learn_draw): the
+        multi-tick launch appends the worlds' transitions in the order their workgroups reach an atomic counter, so two identical
+        runs hold the same transitions in other slots; these draws pick rows by a key of their content -- uniform, with replacement,
+        the same rows in every run.  Device int32 [len(learners), n_steps, batch], queued on the current stream."""
+        n = len(learners)
+        if len({l.batch for l in learners}) != 1:
+            raise ValueError("draw_slots(): the learners of a call must share one batch size")
+        for l in learners:
+            if getattr(l, "keys", None) is None or l.keys.numel() != l.ring["state"].shape[0]:
+                l.keys = torch.zeros(l.ring["state"].shape[0], dtype=torch.int64, device=self.device)
+        arr = (_lib.Learner * n)(*[l.struct() for l in learners])
+        rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
+        keys = (C.c_void_p * n)(*[l.keys.data_ptr() for l in learners])
+        slots = torch.zeros((n, int(n_steps), learners[0].batch), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.rl_learn_draw(self.handle, arr, rings, n, int(n_steps), keys, _ptr(slots), self._stream()), "rl_learn_draw")
+        self.launches += 2
+        return slots
+
+    def learn(self, learners, n_steps, slots=None):
+        """DQNAgent.train() (DQN.py:80-83, 142-153) for every DeviceLearner of `learners` in ONE launch (rl_learn), queued on the current
+        stream behind the ticks launched so far: `n_steps` minibatch updates per brain on its replay ring (learner.ring), then the
+        target copy, and the learner's packed weights rewritten in place -- brains bound with that tensor act on the new weights
+        from the next launch on.  slots: optional int32 [len(learners), n_steps, batch] ring slots (host array or device tensor);
+        None = drawn on the device, uniformly WITH replacement (learn.philox_slots gives the same numbers on the host; the
+        brain index of the draw is the learner's position in `learners`)."""
+        if not learners:
+            return
+        n = len(learners)
+        if n > _lib.MAX_CAPTURE_BRAINS:
+            raise ValueError("learn(): at most %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
+        arr = (_lib.Learner * n)(*[l.struct() for l in learners])
+        rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
+        if slots is not None:
+            if not (torch.is_tensor(slots) and slots.is_cuda):
+                slots = torch.as_tensor(np.array(slots.cpu().numpy() if torch.is_tensor(slots) else slots, dtype=np.int32), device=self.device)
+            slots = slots.to(device=self.device, dtype=torch.int32).contiguous()
+            if slots.numel() != n * n_steps * learners[0].batch or len({l.batch for l in learners}) != 1:
+                raise ValueError("learn(): slots must hold [n_learners, n_steps, batch] = [%d, %d, %d] entries" % (n, n_steps, learners[0].batch))
+        _lib.check(self.lib.rl_learn(self.handle, arr, rings, n, int(n_steps), _ptr(slots), self._stream()), "rl_learn")
+        self._learn_keep = slots   # (the launch reads the table asynchronously)
+        self.launches += 1
+
     def reset_tracking(self):
         if self._trk_dirty:   # (fresh accumulators are zero: a new Environment's first launch is not preceded by three memsets)
             self.trk_sum.zero_(); self.trk_cnt.zero_(); self.trk_pop[:, 1:].zero_()
