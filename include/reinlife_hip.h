@@ -16,6 +16,8 @@
  *   rl_render          Visualize.render()'s drawing of one frame, for any set of worlds     Helpers/render.py:51-239
  *   rl_learn           DQNAgent.train(): the size gate, 5 minibatch updates (smooth-L1, Adam) and the target copy
  *                      Models/DQN.py:80-83, 142-153 (sampling: :99-113, with replacement here)
+ *   rl_learn_dueling   D3QNAgent.train(): one minibatch update of the dueling network (MSE, Adam), batch up to 64
+ *                      Models/D3QN.py:97-116, 148-165 (schedule and target copy of :118-126: the caller's)
  *
  * Conventions
  *   - extern "C", plain pointers and sizes; no torch / C++ types.  `stream` is a hipStream_t passed as void*.
@@ -336,6 +338,32 @@ int rl_learn_supported(int kind);
 int rl_learn(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, const int32_t* slots,
              void* stream);
 
+/* 1 for the brain kinds rl_learn_dueling trains (RL_D3QN), 0 for the others.  RL_PERD3QN has the same network but learns from a
+ * prioritised memory with an importance-weighted loss (PERD3QN.py), which this entry point does not make: 0. */
+int rl_learn_dueling_supported(int kind);
+/* D3QNAgent.train() (Models/D3QN.py:97-116) for n_learners brains in ONE stream-ordered launch, one workgroup per brain, on the same
+ * rl_learner / rl_replay structures as rl_learn (kind must be RL_D3QN: anything else is RL_E_UNSUPPORTED naming the kind; batch in
+ * [1,64]; every other validation is rl_learn's).  rl_learn, rl_learn_supported and rl_learn_draw are unchanged by it.
+ *   network     dueling_ddqn (D3QN.py:148-165), state-dict order fc 153->128, adv_fc1 128->128, adv_fc2 128->8, value_fc1 128->128,
+ *               value_fc2 128->1: 53,897 parameters.  q[i][a] = adv[i][a] + val[i] - M with M the mean of adv over ALL rows and actions
+ *               of the minibatch (D3QN.py:165 writes advantage.mean(), not a per-row mean; the acting kernels' per-row mean is the same
+ *               expression at batch 1).  The target network's q' takes its own M' over the batch's state_prime rows.
+ *   size gate   size = min(*ring.count, ring.capacity), read on the device; size <= min_size: no update.  The reference has no gate but
+ *               random.sample's need of batch rows (D3QN.py:98, 140): min_size = batch - 1.
+ *   n_steps     sequential minibatch updates (the reference: 1 per train()), each: y_i = reward_i + gamma (1 - done_i) max_a q'_target
+ *               (D3QN.py:107-110), loss = mean_i (q[i][a_i] - y_i)^2 (nn.MSELoss, D3QN.py:63, 112), its gradient through both branches
+ *               and the shared fc, and torch.optim.Adam's update exactly as rl_learn makes it (bias corrections in double from
+ *               state[0]; lr, beta1, beta2 re-read as decimals).  loss[s] and grad[s][n_params] are written when given.
+ *   rows        as rl_learn: slots != NULL is device int32 [n_learners][n_steps][batch], all range-checked before the first row is
+ *               fetched (a bad one: error-flag code 6, that brain leaves with NONE of its buffers written, the others train);
+ *               slots == NULL draws with the same Philox mapping and RL_SITE_LEARN.
+ *   afterwards  sync_target != 0: target <- params (the caller's schedule: D3QN.py:125-126 copies every soft_update_freq episodes, and
+ *               D3QN.py:121 trains only once n_epi > exploration); state[0] += updates made; state[1] += 1; `packed` is rewritten from the
+ *               final params, bit for bit what rl_policy_pack_weights(RL_D3QN, ...) makes of them.
+ * Deterministic like rl_learn: plain f32 FMA, every sum by one thread in a fixed order, no float atomics. */
+int rl_learn_dueling(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, const int32_t* slots,
+                     void* stream);
+
 /* The `slots` of an rl_learn call drawn so that they do not depend on the ORDER of a ring's rows: rl_run_ex / rl_capture_transitions
  * append every world's transitions with an atomic add on the ring's counter, so two identical runs hold the same transitions in other
  * slots, and rl_learn's own draw (slots == NULL), which names slots, would train them differently.  Here every row gets a 64-bit key of
@@ -344,6 +372,9 @@ int rl_learn(rl_world* h, const rl_learner* learners, const rl_replay* rings, in
  * whatever slots they sit in (equal rows are interchangeable; distinct rows with equal keys: 2^-64).
  *   keys    host array [n_learners] of device uint64 [ring capacity] scratch, rewritten by every call
  *   slots   device int32, the learners' [n_steps][batch] tables laid end to end (what rl_learn takes when all batches are equal)
+ *           The table is FLAT (draw d = s * batch + j), and batch is at most 32 here: a batch-64 table for rl_learn_dueling,
+ *           [n_steps][64], is the same table as [2 n_steps][32] -- ask with batch = the largest divisor of the real batch that is
+ *           <= 32 and n_steps scaled to match (DeviceWorlds.draw_slots does).
  * Two launches (keys of the rows a ring holds, then one workgroup per draw); call it in front of rl_learn on the same stream.  What it
  * cannot mend: a launch that appends MORE than a ring's capacity overwrites its own rows in append order -- which rows survive then
  * differs from run to run. */

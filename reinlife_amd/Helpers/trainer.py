@@ -19,7 +19,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
             print_results=True, max_agents=100, render=False, static_families=True, training=True, save=True,
             limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None, seed=0, rng=None, per_agent_api=False,
             fused=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
-            learn_steps=5):
+            learn_steps=5, learn_kinds=None):
     """Extra keyword-only arguments: n_worlds / device / seed / rng / synthetic_agents / refill_below (Environment); per_agent_api=True makes the reference's literal
     per-agent get_action / learn calls; fused (default: True for rng="philox" without per_agent_api) runs the loop through
     Environment.run -- whole chunks of ticks per launch, ending where the Tracker closes an interval -- instead of three launches
@@ -42,7 +42,16 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     trains once per `learn_every` ticks of world time, as a single long-lived agent would cause; (2) minibatches are drawn uniformly
     WITH replacement, where the reference's random.sample (DQN.py:100) draws without -- and by a key of the rows' content mixed with
     Philox bits rather than by slot, because the worlds append to a ring in a timing-dependent order: a second identical call gives the
-    same parameters bit for bit unless one chunk appends more than a ring holds."""
+    same parameters bit for bit unless one chunk appends more than a ring holds.
+    learn_kinds (default None = ("DQN",): exactly the above): the brain methods that train.  learn_kinds=("DQN", "D3QN") also trains every
+    D3QN brain, through rl_learn_dueling: its ring holds brain.capacity rows (10,000, D3QN.py:62); after an episode `last` that is a
+    multiple of `learn_every` (default: the smallest train_freq of all learners) and greater than brain.exploration (D3QN.py:121) one
+    launch makes ONE minibatch update (D3QNAgent.train(), D3QN.py:97-116: batch 64, gamma 0.99, lr 1e-3, MSE with the reference's
+    batch-wide advantage mean, Adam) as soon as the ring holds 64 rows; the target network is synced in that launch iff a multiple of
+    brain.soft_update_freq lies in (last - learn_every, last] (D3QN.py:125-126).  The DQN learners' call is a separate launch and draws
+    what it draws without D3QN learners.  The same two deviations apply.  learn_steps: an int is the DQN learners' count; a dict by
+    method name ({"DQN": 5, "D3QN": 1}) sets it per kind.  A name no entry point trains (PERD3QN, PPO, PERDQN), or learn_kinds without
+    learn="device", is a ValueError before a device is touched."""
     if learn == "device" and (per_agent_api or fused is False):
         raise ValueError("trainer(learn='device') needs the fused path (fused=True, per_agent_api=False): the replay rings are filled "
                          "inside the multi-tick launches")
@@ -51,7 +60,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
                       interactive_results=visualize_results, google_colab=google_colab, training=training,
                       limit_reproduction=limit_reproduction, incentivize_killing=incentivize_killing, n_worlds=n_worlds,
                       device=device, seed=seed, rng=rng, synthetic_agents=synthetic_agents, refill_below=refill_below, dist=dist,
-                      world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps)
+                      world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps, learn_kinds=learn_kinds)
     env.reset()
     if fused is None:
         fused = env.rng == "philox" and not per_agent_api

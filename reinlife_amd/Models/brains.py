@@ -5,7 +5,7 @@ batched over all agents through Environment.act(), or one state at a time throug
 
 The per-agent learn() of the reference's brains is accepted and ignored, so that trainer() loops written for the reference keep
 running (a warning is issued once).  DQN brains learn on the device instead, through trainer(learn="device") / learn.DeviceLearner
-(rl_learn); the other kinds stay frozen.
+(rl_learn), and D3QN brains with learn_kinds=("DQN", "D3QN") (rl_learn_dueling); the other kinds stay frozen.
 """
 import random
 import warnings
@@ -151,8 +151,9 @@ class DQNAgent(_HipBrain):
 
 class _DuelingAgent(_HipBrain):
     def __init__(self, method, input_dim, output_dim, exploration, soft_update_freq, train_freq, batch_size, gamma,
-                 load_model, training):
+                 load_model, training, learning_rate=1e-3, capacity=10000):
         super().__init__(input_dim, output_dim, method)
+        self.learning_rate, self.capacity = learning_rate, capacity   # (read by learn.DeviceLearner / Environment; D3QN.py:61-62)
         self.target_net = _Dueling(input_dim, output_dim)
         self.eval_net = _Dueling(input_dim, output_dim)
         self.eval_net.load_state_dict(self.target_net.state_dict())
@@ -214,7 +215,7 @@ class D3QNAgent(_DuelingAgent):
     def __init__(self, input_dim=153, output_dim=8, exploration=1000, soft_update_freq=200, train_freq=20,
                  learning_rate=1e-3, gamma=0.99, batch_size=64, capacity=10000, load_model=False, training=True):
         super().__init__("D3QN", input_dim, output_dim, exploration, soft_update_freq, train_freq, batch_size, gamma,
-                         load_model, training)
+                         load_model, training, learning_rate, capacity)
 
 
 class PERD3QNAgent(_DuelingAgent):
@@ -223,7 +224,7 @@ class PERD3QNAgent(_DuelingAgent):
     def __init__(self, input_dim=153, output_dim=8, exploration=1000, soft_update_freq=200, train_freq=20,
                  learning_rate=1e-3, batch_size=64, capacity=10000, gamma=0.99, load_model=False, training=True):
         super().__init__("PERD3QN", input_dim, output_dim, exploration, soft_update_freq, train_freq, batch_size, gamma,
-                         load_model, training)
+                         load_model, training, learning_rate, capacity)
 
 
 class PPOAgent(_HipBrain):

@@ -158,11 +158,32 @@ class Environment:
                  static_families=True, interactive_results=False, google_colab=False, training=True, save=False,
                  pastel_colors=False, limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None,
                  seed=0, rng=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
-                 learn_steps=5):
+                 learn_steps=5, learn_kinds=None):
         if not brains:
             raise ValueError("Environment needs a non-empty list of brains")
         if learn not in (None, "device"):
             raise ValueError("learn must be None (the brains stay as they are) or 'device' (DQN brains train through rl_learn), got %r" % (learn,))
+        # learn_kinds: the brain methods that train under learn="device".  None = ("DQN",): what learn="device" always did; "D3QN" is an
+        # explicit opt-in (rl_learn_dueling).  Checked here, before a device is touched.
+        from ..learn import ENTRY_BY_METHOD
+        if learn_kinds is not None and learn != "device":
+            raise ValueError("learn_kinds needs learn='device' (got learn=%r)" % (learn,))
+        self.learn_kinds = ("DQN",) if learn_kinds is None else ((learn_kinds,) if isinstance(learn_kinds, str) else tuple(learn_kinds))
+        unknown = [k for k in self.learn_kinds if k not in ENTRY_BY_METHOD]
+        if unknown or not self.learn_kinds:
+            raise ValueError("learn_kinds: no entry point trains %s brains; the kinds that learn on the device are %s"
+                             % (", ".join(map(str, unknown)) or "()", ", ".join(sorted(ENTRY_BY_METHOD))))
+        # learn_steps: minibatch updates per call -- an int is the DQN learners' (as always), a dict by method name sets it per kind;
+        # D3QN defaults to 1 (D3QNAgent.train() makes one update)
+        self.learn_steps_of = {"DQN": 5, "D3QN": 1}
+        if isinstance(learn_steps, dict):
+            bad = [k for k in learn_steps if k not in ENTRY_BY_METHOD]
+            if bad:
+                raise ValueError("learn_steps: no entry point trains %s brains" % ", ".join(map(str, bad)))
+            self.learn_steps_of.update({k: int(v) for k, v in learn_steps.items()})
+        else:
+            self.learn_steps_of["DQN"] = int(learn_steps)
+        learn_steps = self.learn_steps_of["DQN"]
         self.width, self.height = width, height
         self.actions, self.entities = Actions, EntityTypes
         self.brains = brains
@@ -216,7 +237,7 @@ class Environment:
                 raise ValueError("learn='device' runs on a single rank: multi-rank training needs a weight collective (world size %d)" % self.world_size)
             if len(brains) > _lib.MAX_CAPTURE_BRAINS:
                 raise ValueError("learn='device' captures transitions for at most %d brains (got %d)" % (_lib.MAX_CAPTURE_BRAINS, len(brains)))
-            if self.learn_steps < 1 or (learn_every is not None and int(learn_every) < 1):
+            if min(self.learn_steps_of.values()) < 1 or (learn_every is not None and int(learn_every) < 1):
                 raise ValueError("learn_steps and learn_every must be >= 1")
         self.best_agents = []
         # environment.py:118: the painter is built first (pastel colours draw from `random` here, its background tiles at
@@ -247,18 +268,23 @@ class Environment:
         if learn == "device":
             # the replay rings of DQN.py:15 (buffer_limit), filled inside the multi-tick launches; one learner per brain rl_learn trains,
             # whose packed tensor IS that brain's acting weights from here on (rl_learn rewrites it in place)
-            from ..learn import BUFFER_LIMIT, DeviceLearner
-            self.worlds.enable_capture(BUFFER_LIMIT)
-            lib = _lib.lib()
-            for k, b in enumerate(brains):
-                if lib.rl_learn_supported(b.kind):
-                    self.learners[k] = DeviceLearner(b, self.worlds.device, ring=self.worlds.replays[k])
+            from ..learn import BUFFER_LIMIT, DeviceLearner, entry_of
+            entries = {k: entry_of(b.kind) for k, b in enumerate(brains) if b.method in self.learn_kinds}
+            entries = {k: e for k, e in entries.items() if e is not None}
+            if any(e == "rl_learn_dueling" for e in entries.values()):
+                # a D3QN learner's ring holds its brain's `capacity` rows (D3QN.py:62: 10,000); every other ring stays DQN.py:15's
+                self.worlds.enable_capture([int(b.capacity) if entries.get(k) == "rl_learn_dueling" else BUFFER_LIMIT for k, b in enumerate(brains)])
+            else:
+                self.worlds.enable_capture(BUFFER_LIMIT)
+            for k in entries:
+                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k])
             if not self.learners:
-                raise ValueError("learn='device': none of the brains is of a kind rl_learn trains (DQN)")
+                raise ValueError("learn='device': none of the brains is of a kind rl_learn trains (DQN)" if self.learn_kinds == ("DQN",) else
+                                 "learn='device': none of the brains is of a kind in learn_kinds %r" % (self.learn_kinds,))
             self.learn_every = int(learn_every) if learn_every is not None else min(l.train_freq for l in self.learners.values())
             frozen = ["%d (%s)" % (k, b.method) for k, b in enumerate(brains) if k not in self.learners]
             if frozen:
-                warn_inference_only(frozen)
+                warn_inference_only(frozen, self.learn_kinds)
         elif training:
             warn_inference_only()
 
@@ -542,16 +568,40 @@ class Environment:
         if not self.learners:
             return "as loaded / initialised -- reinlife_amd runs inference only, learn() is a no-op"
         frozen = [k for k in range(len(self.brains)) if k not in self.learners]
-        return ("brains %s trained on the device (rl_learn: %d minibatch updates every %d episodes, rows drawn by content key with replacement)"
-                % (sorted(self.learners), self.learn_steps, self.learn_every)
-                + ("; brains %s as loaded / initialised (their kinds do not learn in this build)" % frozen if frozen else ""))
+        dqn = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn")
+        duel = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_dueling")
+        note = []
+        if dqn:
+            note.append("brains %s trained on the device (rl_learn: %d minibatch updates every %d episodes, rows drawn by content key with replacement)"
+                        % (dqn, self.learn_steps, self.learn_every))
+        if duel:
+            note.append("brains %s trained on the device (rl_learn_dueling: %d minibatch update(s) of batch %s every %d episodes once past the brain's "
+                        "exploration, target synced every soft_update_freq episodes, rows drawn by content key with replacement)"
+                        % (duel, self.learn_steps_of["D3QN"], sorted({self.learners[k].batch for k in duel}), self.learn_every))
+        if frozen:
+            note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if duel else
+                        "brains %s as loaded / initialised (their kinds do not learn in this build)" % frozen)
+        return "; ".join(note)
 
-    def learn_now(self):
-        """One DQNAgent.train() (DQN.py:80-83) for every learner, queued behind the ticks launched so far (DeviceWorlds.learn).  The
-        minibatches are drawn by the rows' content (DeviceWorlds.draw_slots): the rings' order differs from run to run, the run does not."""
-        if self.learners:
-            ls = [self.learners[k] for k in sorted(self.learners)]
-            self.worlds.learn(ls, self.learn_steps, slots=self.worlds.draw_slots(ls, self.learn_steps))
+    def learn_now(self, last=None):
+        """One DQNAgent.train() (DQN.py:80-83) for every DQN learner, queued behind the ticks launched so far (DeviceWorlds.learn).  The
+        minibatches are drawn by the rows' content (DeviceWorlds.draw_slots): the rings' order differs from run to run, the run does not.
+        D3QN learners (learn_kinds) train in a call of their own behind it -- the DQN learners' call and draws are what they are without
+        them: D3QNAgent.learn's schedule (D3QN.py:118-126) at this build's granularity.  `last` is the episode just finished: a learner
+        trains only once last > brain.exploration, and its target is synced in this call iff a multiple of brain.soft_update_freq lies
+        in (last - learn_every, last].  last=None: every D3QN learner trains, sync_target as the learner holds it."""
+        dqn = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn"]
+        if dqn:
+            self.worlds.learn(dqn, self.learn_steps, slots=self.worlds.draw_slots(dqn, self.learn_steps))
+        duel = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_dueling"
+                and (last is None or last > self.learners[k].exploration)]
+        n = self.learn_steps_of["D3QN"]
+        for batch in sorted({l.batch for l in duel}):   # (one call per batch size: a call's slot table is rectangular)
+            ls = [l for l in duel if l.batch == batch]
+            if last is not None:
+                for l in ls:
+                    l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
+            self.worlds.learn(ls, n, slots=self.worlds.draw_slots(ls, n))
 
     def sync_learners(self):
         """The trained parameters into the brains' modules (DeviceLearner.sync_to_module): what Saver and state_dict() read."""
@@ -594,7 +644,7 @@ class Environment:
             self._refresh(after="update")
             last = n_epi + k - 1
             if self.learners and last > 0 and last % self.learn_every == 0:
-                self.learn_now()
+                self.learn_now(last)
             if self.training and last > 0 and last % interval == 0:
                 self.tracker.update_results(None, last, defer=True)   # the device half of the close: queued behind the chunk
             n_epi += k
@@ -695,11 +745,16 @@ def resolve_dist(dist=None):
     return None, 0, 1
 
 
-def warn_inference_only(frozen=None):
+def warn_inference_only(frozen=None, kinds=("DQN",)):
     import warnings
     if frozen is not None:
-        warnings.warn("learn='device' trains the DQN brains of this run; brains %s are of kinds rl_learn does not train yet: they stay "
-                      "inference only -- brain.learn() is a no-op for them and their weights are NOT updated." % ", ".join(frozen), stacklevel=3)
+        if tuple(kinds) == ("DQN",):
+            warnings.warn("learn='device' trains the DQN brains of this run; brains %s are of kinds rl_learn does not train yet: they stay "
+                          "inference only -- brain.learn() is a no-op for them and their weights are NOT updated (D3QN brains learn with "
+                          "learn_kinds=('DQN', 'D3QN'))." % ", ".join(frozen), stacklevel=3)
+        else:
+            warnings.warn("learn='device' trains the %s brains of this run; brains %s are of other kinds (or of kinds no entry point trains): they stay "
+                          "inference only -- brain.learn() is a no-op for them and their weights are NOT updated." % (" and ".join(kinds), ", ".join(frozen)), stacklevel=3)
         return
     warnings.warn("reinlife_amd runs ReinLife's per-tick path (world tick + policy inference) only: training=True keeps the "
                   "reference's loop, epsilon schedules and Tracker, but brain.learn() is a no-op and the brains' weights are NOT "

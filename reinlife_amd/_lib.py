@@ -111,6 +111,8 @@ ABI = [
     ("rl_policy_act", C.c_int, [_P, C.POINTER(Brain), C.c_int, _P, _P, _P, _P, _P]),
     ("rl_learn_supported", C.c_int, [C.c_int]),
     ("rl_learn", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_dueling_supported", C.c_int, [C.c_int]),
+    ("rl_learn_dueling", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, C.POINTER(_P), _P, _P]),
     ("rl_render", C.c_int, [_P, C.POINTER(RenderStyle), _P, C.c_int, _P, _P]),
     ("rl_set_option", C.c_int, [C.c_char_p, C.c_char_p]),

@@ -15,11 +15,11 @@ TUNE = bool(os.environ.get("RL_TUNE"))
 TAG = "_prof" if PROFILE else "_tune" if TUNE else ("_" + os.environ["RL_LIB_TAG"] if os.environ.get("RL_LIB_TAG") else "")
 TUNE_LIB_PATH = os.path.join(LIB_DIR, "libreinlife_hip_tune.so")
 LIB_PATH = os.path.join(LIB_DIR, "libreinlife_hip%s.so" % TAG)
-SOURCES = ["rl_world.hip", "rl_run.hip", "rl_policy.hip", "rl_render.hip", "rl_learn.hip", "rl_capi.hip"]
+SOURCES = ["rl_world.hip", "rl_run.hip", "rl_policy.hip", "rl_render.hip", "rl_learn.hip", "rl_learn_dueling.hip", "rl_capi.hip"]
 # (object suffix, extra flags) per source: rl_run.hip is compiled as TWO units side by side (RL_RUN_UNIT, see the file) -- one compiler for all
 # of k_run's instantiations is what a forced build waits for
 UNITS = {"rl_run.hip": [("", ["-DRL_RUN_UNIT=0"]), ("_all", ["-DRL_RUN_UNIT=1"])]}
-HEADERS = ["rl_common.h", "rl_policy_dev.h", "rl_world_dev.h", os.path.join("..", "..", "include", "reinlife_hip.h")]
+HEADERS = ["rl_common.h", "rl_policy_dev.h", "rl_world_dev.h", "rl_learn_dev.h", os.path.join("..", "..", "include", "reinlife_hip.h")]
 # -ffp-contract=off: the world kernels' float64 reward / fitness arithmetic must round exactly like the CPU path
 # -fvisibility=hidden: the export list is include/reinlife_hip.h (its declarations sit inside a visibility push(default))
 # --offload-compress: the gfx950 code objects are stored zstd-compressed in the fat binary (2.8 MB -> 0.7 MB; the runtime inflates them once, at load)

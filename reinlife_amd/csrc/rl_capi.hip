@@ -30,6 +30,8 @@ int rl_render_launch(rl_world*, const rl_render_style*, const int32_t*, int, uin
 int rl_learn_supported_impl(int);
 int rl_learn_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, const int32_t*, hipStream_t);
 int rl_learn_draw_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, unsigned long long* const*, int32_t*, hipStream_t);
+int rl_learn_dueling_supported_impl(int);
+int rl_learn_dueling_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, const int32_t*, hipStream_t);
 
 static thread_local char g_err[512] = "";
 
@@ -410,6 +412,26 @@ int rl_learn(rl_world* h, const rl_learner* learners, const rl_replay* rings, in
     }
     DeviceGuard guard(device_of_pointer(learners[0].params));
     return rl_learn_launch(h, learners, rings, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+int rl_learn_dueling_supported(int kind) { return rl_learn_dueling_supported_impl(kind); }
+
+int rl_learn_dueling(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, const int32_t* slots, void* stream)
+{
+    if (!h) { rl_set_error("rl_learn_dueling: null handle"); return RL_E_INVALID; }
+    if (!learners || !rings) { rl_set_error("rl_learn_dueling: null learners / rings"); return RL_E_INVALID; }
+    if (n_learners < 1 || n_learners > RL_MAX_CAPTURE_BRAINS) { rl_set_error("rl_learn_dueling: n_learners must be in [1,%d] (got %d)", RL_MAX_CAPTURE_BRAINS, n_learners); return RL_E_INVALID; }
+    if (n_steps < 1) { rl_set_error("rl_learn_dueling: n_steps must be >= 1 (got %d)", n_steps); return RL_E_INVALID; }
+    for (int i = 0; i < n_learners; ++i) {
+        const rl_learner& l = learners[i];
+        const rl_replay& r = rings[i];
+        if (!rl_learn_dueling_supported_impl(l.kind)) { rl_set_error("rl_learn_dueling: learner %d has brain kind %d; this entry point trains RL_D3QN (1) only (rl_learn_dueling_supported)", i, l.kind); return RL_E_UNSUPPORTED; }
+        if (!l.params || !l.target || !l.adam_m || !l.adam_v || !l.state || !l.packed) { rl_set_error("rl_learn_dueling: learner %d: params / target / adam_m / adam_v / state / packed must not be null", i); return RL_E_INVALID; }
+        if (l.batch < 1 || l.batch > 64) { rl_set_error("rl_learn_dueling: learner %d: batch must be in [1,64] (got %d)", i, l.batch); return RL_E_INVALID; }
+        if (!r.state || !r.state_prime || !r.action || !r.reward || !r.done || !r.count || r.capacity < 1 || r.capacity > 0x7fffffff) { rl_set_error("rl_learn_dueling: replay %d incomplete (state / state_prime / action / reward / done / count, capacity in [1, 2^31))", i); return RL_E_INVALID; }
+    }
+    DeviceGuard guard(device_of_pointer(learners[0].params));
+    return rl_learn_dueling_launch(h, learners, rings, n_learners, n_steps, slots, (hipStream_t)stream);
 }
 
 int rl_learn_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, unsigned long long* const* keys,

@@ -23,10 +23,7 @@
 //   packing   after the last step the workgroup rewrites `packed` from the final parameters: a port of rl_policy.hip's pack_in_layer /
 //             pack_hidden_layer / pack_head / write_epilogue_consts for the toward-zero split, bit for bit (integer code, one multiply
 //             by a power of two, one exact subtraction).
-#include "rl_policy_dev.h"
-
-#include <stdio.h>
-#include <stdlib.h>
+#include "rl_learn_dev.h"
 
 namespace {
 
@@ -93,23 +90,6 @@ __device__ inline void learn_forward(const float* W, const float* bias, const fl
     for (int r = 0; r < RPT; ++r) H[(row0 + r) * HS + f] = RELU ? fmaxf(acc[r], 0.0f) : acc[r];
 }
 
-struct AdamStep {
-    float *p, *m, *v, *grad;   // grad: this step's row of the caller's buffer or null
-    float w1, w2, beta2, bc2_sqrt, eps, neg_step;
-};
-// torch.optim.Adam's single-tensor update: exp_avg.lerp_(g, 1 - b1); exp_avg_sq.mul_(b2).addcmul_(g, g, value = 1 - b2);
-// denom = exp_avg_sq.sqrt() / sqrt(1 - b2^t) + eps; param.addcdiv_(exp_avg, denom, value = -lr / (1 - b1^t))
-__device__ inline void adam_update(const AdamStep& a, int idx, float g)
-{
-    if (a.grad) a.grad[idx] = g;
-    float m = a.m[idx], v = a.v[idx];
-    m = m + a.w1 * (g - m);
-    v = v * a.beta2 + (a.w2 * g) * g;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    a.m[idx] = m; a.v[idx] = v;
-    a.p[idx] = a.p[idx] + (a.neg_step * m) / denom;
-}
-
 // dW[o][k] = sum_rows D[row][o] * IN[row][k] (rows ascending) and Adam at once.  A work item is (a chunk of 16 outputs, one k):
 // consecutive threads take consecutive k, so the parameter traffic of a chunk row is contiguous.
 template <int NIN, int NOUT, int DS, int INS>
@@ -144,37 +124,6 @@ __device__ inline void learn_bgrad(const AdamStep& a, int off, const float* D, i
         adam_update(a, off + tid, g);
     }
 }
-
-// ---- the toward-zero f16 split of rl_policy.hip's host packer (f16_rtz, f16_to_float, split2_host), on the device ----
-__device__ inline uint32_t learn_f16_rtz(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    const int e = (int)((u >> 23) & 0xff) - 127;
-    const uint32_t man = u & 0x7fffffu;
-    if (e < -24) return sign;
-    if (e < -14) return sign | ((man | 0x800000u) >> (13 + (-14 - e)));
-    return sign | (uint32_t)((e + 15) << 10) | (man >> 13);
-}
-__device__ inline float learn_f16_to_float(uint32_t h)
-{
-    const uint32_t sign = (h & 0x8000u) << 16, e = (h >> 10) & 0x1f, man = h & 0x3ffu;
-    if (e == 0) return __uint_as_float(__float_as_uint((float)man * (1.0f / 16777216.0f)) | sign);
-    return __uint_as_float(sign | ((e - 15 + 127) << 23) | (man << 13));
-}
-// one fragment of 8 scaled weights -> its hi and lo planes (16 bytes each)
-__device__ inline void learn_store_fragment(const float (&x)[8], uint4* hi_dst, uint4* lo_dst)
-{
-    uint32_t hi[8], lo[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        hi[e] = learn_f16_rtz(x[e]);
-        lo[e] = learn_f16_rtz(x[e] - learn_f16_to_float(hi[e]));   // (the subtraction is exact)
-    }
-    *hi_dst = uint4{hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16)};
-    *lo_dst = uint4{lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16)};
-}
-__device__ inline int learn_hidden_k(int t, int c, int e, int lane) { const int r = 8 * c + e; return 32 * t + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // rl_policy_pack_weights(RL_DQN, P) -> packed, by the whole workgroup.  sc / un: LDS [200] each (features of fc1, fc2, fc3).
 __device__ inline void learn_pack_dqn(const float* P, float* packed, float* sc, float* un, int tid)
@@ -475,15 +424,6 @@ __global__ __launch_bounds__(256) void k_learn_pick(const DrawArgs A)
         for (int b = 0; b < brain; ++b) batch0 += A.n_steps * A.b[b].batch;
         A.slots[batch0 + d] = size > 0 ? best_i[0] : 0;
     }
-}
-
-// The decimal a float hyperparameter stands for (0.999f -> 0.999, not 0.99900001287): torch computes Adam's bias corrections from the
-// Python doubles, and 1 - 0.999f^t differs from 1 - 0.999^t by 1.3e-5 of itself at t = 1.
-double learn_decimal(float f)
-{
-    char buf[40];
-    snprintf(buf, sizeof(buf), "%.7g", (double)f);
-    return strtod(buf, nullptr);
 }
 
 }  // namespace

@@ -1,11 +1,16 @@
-"""DeviceLearner: what a DQN brain needs to learn on the device (rl_learn, include/reinlife_hip.h) -- the flat f32 master parameters,
+"""DeviceLearner: what a DQN or D3QN brain needs to learn on the device (rl_learn / rl_learn_dueling, include/reinlife_hip.h) -- the flat f32 master parameters,
 the target network, Adam's moments, the step / call counters and the packed weights the acting kernels read, all as device tensors.
 
 Reference: DQNAgent owns `agent`, `target`, `memory` and `optimizer` (ReinLife/Models/DQN.py:48-52); train() (DQN.py:80-83, 142-153)
 samples 5 minibatches of 32 and makes one Adam step on each, then copies agent -> target.  Here the replay memory is the brain's
 rl_replay ring (DeviceWorlds.enable_capture) and the five steps are ONE launch (DeviceWorlds.learn).  Two deviations, stated wherever
 this is documented: minibatches are drawn WITH replacement (the reference's random.sample draws without), and the schedule of train()
-calls is the caller's (Environment: once per `learn_every` episodes), not "whenever an agent's age is a multiple of train_freq"."""
+calls is the caller's (Environment: once per `learn_every` episodes), not "whenever an agent's age is a multiple of train_freq".
+
+D3QNAgent owns `eval_net`, `target_net`, `buffer` and `optimizer` (ReinLife/Models/D3QN.py:58-62); train() (D3QN.py:97-116) samples ONE
+minibatch of 64 and makes one Adam step on its MSE loss; learn() (D3QN.py:118-126) trains only once n_epi > exploration and copies eval ->
+target every soft_update_freq episodes.  The learner takes lr, gamma, batch, train_freq, exploration and soft_update_freq from the
+brain; its only size gate is random.sample's need of `batch` rows (min_size = batch - 1); the same two deviations apply."""
 import copy
 import ctypes as C
 
@@ -15,28 +20,46 @@ import torch
 from . import _lib
 
 GAMMA, BATCH, MIN_SIZE, BUFFER_LIMIT = 0.98, 32, 1000, 50_000   # DQN.py:14-16, 81
+ENTRY_BY_METHOD = {"DQN": "rl_learn", "D3QN": "rl_learn_dueling"}   # the brain kinds an entry point trains (Environment's learn_kinds)
+
+
+def entry_of(kind):
+    """The name of the C entry point that trains brains of `kind`, or None."""
+    lib = _lib.lib()
+    return "rl_learn" if lib.rl_learn_supported(kind) else "rl_learn_dueling" if lib.rl_learn_dueling_supported(kind) else None
 
 
 class DeviceLearner:
     def __init__(self, brain, device="cuda:0", ring=None):
         lib = _lib.lib()
-        if not lib.rl_learn_supported(brain.kind):
-            raise ValueError("rl_learn does not train %s brains (kind %d): only DQN learns on the device" % (brain.method, brain.kind))
+        self.entry = entry_of(brain.kind)
+        if self.entry is None:
+            raise ValueError("no entry point trains %s brains (kind %d): only DQN (rl_learn) and D3QN (rl_learn_dueling) learn on the device"
+                             % (brain.method, brain.kind))
         from .worlds import pack_brain_weights
         self.brain, self.kind, self.device = brain, brain.kind, torch.device(device)
         flat = brain.state_dict_flat()
         self.n_params = int(lib.rl_policy_n_params(self.kind))
         self.params = torch.as_tensor(flat, device=self.device)
-        self.target = self.params.clone()                       # DQN.py:50
+        self.target = self.params.clone()                       # DQN.py:50 / D3QN.py:60
         self.adam_m = torch.zeros_like(self.params)
         self.adam_v = torch.zeros_like(self.params)
         self.state = torch.zeros(2, dtype=torch.int64, device=self.device)   # [Adam steps taken, rl_learn calls made]
         self.packed = pack_brain_weights(self.kind, flat, self.device)
-        self.lr = float(getattr(brain, "learning_rate", 0.0005))
         self.train_freq = int(getattr(brain, "train_freq", 20))
-        self.gamma, self.batch, self.min_size = GAMMA, BATCH, MIN_SIZE
-        self.beta1, self.beta2, self.eps = 0.9, 0.999, 1e-8      # torch.optim.Adam's defaults (DQN.py:52)
-        self.sync_target = True                                  # DQN.py:83
+        if self.entry == "rl_learn":
+            self.lr = float(getattr(brain, "learning_rate", 0.0005))
+            self.gamma, self.batch, self.min_size = GAMMA, BATCH, MIN_SIZE
+            self.n_steps_default = 5                             # DQN.py:143
+            self.sync_target = True                              # DQN.py:83
+        else:   # D3QN.py:54-72: the brain's own hyperparameters
+            self.lr = float(getattr(brain, "learning_rate", 1e-3))
+            self.gamma, self.batch = float(getattr(brain, "gamma", 0.99)), int(getattr(brain, "batch_size", 64))
+            self.min_size = self.batch - 1                       # random.sample needs `batch` rows (D3QN.py:98, 140): the only gate
+            self.exploration, self.soft_update_freq = int(getattr(brain, "exploration", 1000)), int(getattr(brain, "soft_update_freq", 200))
+            self.n_steps_default = 1                             # D3QNAgent.train() makes one update
+            self.sync_target = False                             # the schedule's (D3QN.py:125-126, Environment.learn_now)
+        self.beta1, self.beta2, self.eps = 0.9, 0.999, 1e-8      # torch.optim.Adam's defaults (DQN.py:52, D3QN.py:61)
         self.ring = ring          # the brain's replay ring: a dict of device tensors as DeviceWorlds.enable_capture() makes them
         self.loss = None          # optional device float32 [n_steps]
         self.grad = None          # optional device float32 [n_steps, n_params] (tests, diagnostics)
@@ -71,7 +94,11 @@ class DeviceLearner:
 
     def sync_to_module(self):
         """The trained parameters into brain.agent and the target network's into brain.target (made on first use: a copy, no
-        generator draw), so that Saver and state_dict() see them."""
+        generator draw), so that Saver and state_dict() see them.  D3QN: into brain.eval_net and brain.target_net."""
+        if self.entry == "rl_learn_dueling":
+            self._load(self.brain.eval_net, self.params.cpu().numpy())
+            self._load(self.brain.target_net, self.target.cpu().numpy())
+            return
         self._load(self.brain.agent, self.params.cpu().numpy())
         if getattr(self.brain, "target", None) is None:
             self.brain.target = copy.deepcopy(self.brain.agent)

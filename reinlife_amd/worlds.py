@@ -387,11 +387,14 @@ class DeviceWorlds:
 
     def enable_capture(self, capacity, with_prob=False):
         """Allocate one replay ring per brain (rl_replay): filled by capture_transitions() after a stand-alone tick, or by run() inside
-        the multi-tick launch (every tick of it)."""
+        the multi-tick launch (every tick of it).  capacity: one number for all rings, or one per brain."""
         self._capture_prob = bool(with_prob)
         self.replays = []
         arr = (_lib.Replay * self.n_brains)()
-        for b in range(self.n_brains):
+        caps = [int(capacity)] * self.n_brains if np.isscalar(capacity) else [int(c) for c in capacity]
+        if len(caps) != self.n_brains or min(caps) < 1:
+            raise ValueError("enable_capture(): capacity must be one positive number or one per brain (%d brains), got %r" % (self.n_brains, capacity))
+        for b, capacity in enumerate(caps):
             r = {"state": torch.zeros((capacity, _lib.OBS_DIM), dtype=torch.float32, device=self.device),
                  "state_prime": torch.zeros((capacity, _lib.OBS_DIM), dtype=torch.float32, device=self.device),
                  "action": torch.zeros(capacity, dtype=torch.int8, device=self.device),
@@ -418,18 +421,26 @@ class DeviceWorlds:
         """Ring slots for learn(learners, n_steps, slots=...) that do not depend on the ORDER of the rings' rows (rl_learn_draw): the
         multi-tick launch appends the worlds' transitions in the order their workgroups reach an atomic counter, so two identical
         runs hold the same transitions in other slots; these draws pick rows by a key of their content -- uniform, with replacement,
-        the same rows in every run.  Device int32 [len(learners), n_steps, batch], queued on the current stream."""
+        the same rows in every run.  Device int32 [len(learners), n_steps, batch], queued on the current stream.
+        rl_learn_draw's table is flat (draw d = s * batch + j) and its batch is at most 32, so for a larger batch (D3QN: 64) the same
+        table is asked for as [n_steps * batch / b][b], b the largest divisor of batch that is <= 32 ([n_steps][64] = [2 n_steps][32])."""
         n = len(learners)
         if len({l.batch for l in learners}) != 1:
             raise ValueError("draw_slots(): the learners of a call must share one batch size")
+        batch = int(learners[0].batch)
+        # any batch in [1, 64] works: a prime one such as 37 draws as [37 n_steps][1] -- more steps of one draw, the same flat table
+        draw_batch = max(b for b in range(1, min(batch, 32) + 1) if batch % b == 0)
+        draw_steps = int(n_steps) * (batch // draw_batch)
         for l in learners:
             if getattr(l, "keys", None) is None or l.keys.numel() != l.ring["state"].shape[0]:
                 l.keys = torch.zeros(l.ring["state"].shape[0], dtype=torch.int64, device=self.device)
         arr = (_lib.Learner * n)(*[l.struct() for l in learners])
+        for a in arr:
+            a.batch = draw_batch
         rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
         keys = (C.c_void_p * n)(*[l.keys.data_ptr() for l in learners])
-        slots = torch.zeros((n, int(n_steps), learners[0].batch), dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.rl_learn_draw(self.handle, arr, rings, n, int(n_steps), keys, _ptr(slots), self._stream()), "rl_learn_draw")
+        slots = torch.zeros((n, int(n_steps), batch), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.rl_learn_draw(self.handle, arr, rings, n, draw_steps, keys, _ptr(slots), self._stream()), "rl_learn_draw")
         self.launches += 2
         return slots
 
@@ -439,10 +450,16 @@ class DeviceWorlds:
         target copy, and the learner's packed weights rewritten in place -- brains bound with that tensor act on the new weights
         from the next launch on.  slots: optional int32 [len(learners), n_steps, batch] ring slots (host array or device tensor);
         None = drawn on the device, uniformly WITH replacement (learn.philox_slots gives the same numbers on the host; the
-        brain index of the draw is the learner's position in `learners`)."""
+        brain index of the draw is the learner's position in `learners`).
+        A list of D3QN learners goes to rl_learn_dueling instead (D3QNAgent.train(), D3QN.py:97-116: batch up to 64, MSE, the target copy
+        only when learner.sync_target says so).  The learners of one call must all belong to one entry point: ValueError otherwise."""
         if not learners:
             return
         n = len(learners)
+        entries = {l.entry for l in learners}
+        if len(entries) != 1:
+            raise ValueError("learn(): the learners of a call must be of one kind (one entry point), got %s" % sorted(entries))
+        entry = entries.pop()
         if n > _lib.MAX_CAPTURE_BRAINS:
             raise ValueError("learn(): at most %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
         arr = (_lib.Learner * n)(*[l.struct() for l in learners])
@@ -453,7 +470,7 @@ class DeviceWorlds:
             slots = slots.to(device=self.device, dtype=torch.int32).contiguous()
             if slots.numel() != n * n_steps * learners[0].batch or len({l.batch for l in learners}) != 1:
                 raise ValueError("learn(): slots must hold [n_learners, n_steps, batch] = [%d, %d, %d] entries" % (n, n_steps, learners[0].batch))
-        _lib.check(self.lib.rl_learn(self.handle, arr, rings, n, int(n_steps), _ptr(slots), self._stream()), "rl_learn")
+        _lib.check(getattr(self.lib, entry)(self.handle, arr, rings, n, int(n_steps), _ptr(slots), self._stream()), entry)
         self._learn_keep = slots   # (the launch reads the table asynchronously)
         self.launches += 1
 
