@@ -64,7 +64,8 @@ enum { RL_F_DEAD = 1, RL_F_REPRODUCED = 2, RL_F_KILLED = 4, RL_F_ATE_SUPER = 8, 
 enum { RL_DQN = 0, RL_D3QN = 1, RL_PERD3QN = 2, RL_PPO = 3, RL_PERDQN = 4 };
 /* Philox draw sites */
 enum { RL_SITE_FOOD = 1, RL_SITE_REPRO = 2, RL_SITE_BIRTH = 3, RL_SITE_PRODUCE = 4, RL_SITE_ACT = 5,
-       RL_SITE_RESET_AGENT = 6, RL_SITE_RESET_FOOD = 7, RL_SITE_RESET_POISON = 8, RL_SITE_RESET_SUPER = 9, RL_SITE_LEARN = 10 };
+       RL_SITE_RESET_AGENT = 6, RL_SITE_RESET_FOOD = 7, RL_SITE_RESET_POISON = 8, RL_SITE_RESET_SUPER = 9, RL_SITE_LEARN = 10,
+       RL_SITE_LEARN_PRIO = 11 };
 
 /* keyword arguments of Environment(...) that matter on the path (environment.py:74-89) */
 typedef struct {
@@ -338,8 +339,9 @@ int rl_learn_supported(int kind);
 int rl_learn(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, const int32_t* slots,
              void* stream);
 
-/* 1 for the brain kinds rl_learn_dueling trains (RL_D3QN), 0 for the others.  RL_PERD3QN has the same network but learns from a
- * prioritised memory with an importance-weighted loss (PERD3QN.py), which this entry point does not make: 0. */
+/* 1 for the brain kinds rl_learn_dueling trains (RL_D3QN), 0 for the others.  RL_PERD3QN has the same network and the same plain MSE
+ * loss but learns from a prioritised memory (PERD3QN.py:110-111, 133-182), which this entry point does not keep: 0
+ * (rl_learn_prioritized trains it). */
 int rl_learn_dueling_supported(int kind);
 /* D3QNAgent.train() (Models/D3QN.py:97-116) for n_learners brains in ONE stream-ordered launch, one workgroup per brain, on the same
  * rl_learner / rl_replay structures as rl_learn (kind must be RL_D3QN: anything else is RL_E_UNSUPPORTED naming the kind; batch in
@@ -380,6 +382,69 @@ int rl_learn_dueling(rl_world* h, const rl_learner* learners, const rl_replay* r
  * differs from run to run. */
 int rl_learn_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps,
                   unsigned long long* const* keys, int32_t* slots, void* stream);
+
+/* ---- prioritised replay (PERD3QN) ------------------------------------------------------------------------------- */
+/* The prioritised memory of one learning PERD3QN brain (PrioritizedReplayBuffer, Models/PERD3QN.py:133-182) beside its rl_replay ring:
+ * caller-owned device buffers.  The ring itself, rl_run_ex and rl_capture_transitions know nothing of priorities: store() gives a new
+ * row max(priorities) (PERD3QN.py:147, 153) and never lowers that maximum (a row overwritten with the maximum keeps it), so between two
+ * learning calls the maximum is a constant and "every row appended since the last draw gets the current maximum" is done after the
+ * fact, from `seen` and the ring's counter (slot = count mod capacity). */
+typedef struct {
+    float* priority;            /* [capacity] */
+    float* weight;              /* [capacity] scratch: priority^alpha, rewritten by every draw */
+    unsigned long long* keys;   /* [capacity] scratch: content keys as rl_learn_draw makes them */
+    float* prio_max;            /* [1] initialise to 1.0 (PERD3QN.py:147: the priority of the first row of an empty memory) */
+    unsigned long long* seen;   /* [1] initialise to 0: ring.count as of the last draw */
+    float alpha;                /* 0.6 (PERD3QN.py:134); must be > 0 */
+} rl_prio;
+/* PrioritizedReplayBuffer.sample's draw (PERD3QN.py:157-165: np.random.choice(len, batch, p = priorities^alpha / sum), WITH replacement)
+ * for n_learners PERD3QN brains, stream-ordered, no host round trip, no allocation; like rl_learn_draw it does not depend on the slots
+ * the rings' rows sit in.  Two launches:
+ *   prepare   per row of [0, size): the slots in [*seen, *ring.count) mod capacity (all of them when count - seen >= capacity) get
+ *             priority = *prio_max; weight = powf(priority, alpha); keys[row] = the row's content key exactly as rl_learn_draw makes it
+ *   pick      one workgroup per draw d = s * batch + j (batch in [1,64] directly): v = mix64(key ^ salt_d), salt_d = words 0-1 of
+ *             rl_philox(seed, 0, i, (uint32)state[1], RL_SITE_LEARN_PRIO, d); U = ((v >> 41) + 0.5) / 2^23, a uniform in (0,1);
+ *             t = -logf(U) / weight; the draw takes the row with the smallest (t, v, slot), compared lexicographically.  An exponential
+ *             race: row i wins with probability w_i / sum w, the same rows whatever slots they sit in (U has 23 bits: rows whose t tie
+ *             are told apart by v, and on a ring of N rows the probabilities are those of the exact race up to about N / 2^23 of
+ *             themselves).  A row of weight 0 (or NaN) has t = +inf and loses to every finite t; so does a row whose positive weight is so
+ *             small that -logf(U) / weight overflows (weight below about 4.9e-38: it ranks with the zero-weight rows; with alpha =
+ *             0.6 no float priority is that small, an alpha above about 0.84 reaches it with denormal priorities).  If EVERY weight is zero the tie-break on
+ *             v makes the draw rl_learn_draw's uniform content-key draw -- the reference would raise there (np.random.choice refuses a p
+ *             of NaNs).  An empty ring draws slot 0.  This launch also advances *seen to *ring.count (the prepare launch is its only reader).
+ *   slots     device int32, the learners' [n_steps][batch] tables laid end to end ([n_learners][n_steps][batch] when all batches are equal)
+ * All n_steps of a call are drawn from the priorities as they stand at the draw: with n_steps = 1 -- the reference's train(), and what
+ * Environment uses -- this is the reference's order exactly; with more, steps 2.. do not see the priorities step 1 will write.
+ * Every learner's kind must be RL_PERD3QN (anything else: RL_E_UNSUPPORTED naming the kind); rings need state / state_prime / action /
+ * reward / done / age / count; every pointer of rl_prio must be set and alpha > 0.
+ * Two deviations from the reference, as for rl_learn_draw: rows appended between two draws all get the maximum as of the earlier
+ * learning call (the reference recomputes it at every store(), but nothing changes it in between), and a launch that appends MORE than a
+ * ring's capacity overwrites its own rows in append order -- which rows survive then differs from run to run. */
+int rl_learn_prioritized_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners,
+                              int n_steps, int32_t* slots, void* stream);
+/* 1 for the brain kinds rl_learn_prioritized trains (RL_PERD3QN), 0 for the others */
+int rl_learn_prioritized_supported(int kind);
+/* PERD3QNAgent.train() (Models/PERD3QN.py:94-115) for n_learners brains in ONE stream-ordered launch: rl_learn_dueling's update, the
+ * same arithmetic in the same order (DuelingDDQN, PERD3QN.py:185-202, is the D3QN network; the advantage mean is the minibatch's), plus
+ * the prioritised memory's upkeep.  What the reference does, stated exactly:
+ *   loss        plain nn.MSELoss (PERD3QN.py:56, 109).  sample() computes importance weights (PERD3QN.py:168-172) but train() never uses
+ *               them, so they -- and beta / beta_increment -- have no effect, there or here.  There is NO importance-weighted loss.
+ *   priorities  after the forward passes, update_priorities(indices, |next_q_value - q_value|) (PERD3QN.py:110-111) with next_q_value =
+ *               max_a q'_target(s') and q_value = q_eval(s)[a], each with its batch-wide mean: the reference's expression, not the TD
+ *               error (no reward, no gamma, no done mask).  Here: right where a step forms td, every batch row writes priority[slot]
+ *               from that step's pre-update parameters; duplicated slots write equal bits; later steps overwrite earlier ones.
+ *   afterwards  as rl_learn_dueling, and, in a call that trained (size > min_size), *prio_max = max(priority[0 .. size)) (what store()
+ *               hands the next new rows, PERD3QN.py:147); a call below the size gate leaves priorities and prio_max alone.
+ *   order       PRECONDITION: rl_learn_prioritized_draw has run on these rings since the last row was appended (the `slots` of this
+ *               call are its output).  The maximum is taken over the rows as they stand: rows the draw has not stamped yet still hold
+ *               stale priorities (zero in a fresh buffer) and would lower it.
+ * Validation is rl_learn_dueling's with these differences: kind must be RL_PERD3QN (anything else: RL_E_UNSUPPORTED naming the kind);
+ * slots == NULL is refused with RL_E_INVALID -- the draw is rl_learn_prioritized_draw's job; prios[i].priority / prio_max / seen must
+ * not be null and alpha > 0.  batch in [1,64].  min_size as before: the reference needs one row only (np.random.choice), min_size = 0.
+ * A slot outside [0, size): error-flag code 6, and NONE of that brain's buffers -- priorities and prio_max included -- is written.
+ * rl_learn, rl_learn_draw, rl_learn_dueling and the two older *_supported answers are unchanged by it. */
+int rl_learn_prioritized(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners, int n_steps,
+                         const int32_t* slots, void* stream);
 
 /* ---- frames ---------------------------------------------------------------------------------------------------- */
 /* What the painter of Helpers/render.py:51-239 draws, as integers: pixels per cell, the body square (offset, side, border width), the

@@ -19,7 +19,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
             print_results=True, max_agents=100, render=False, static_families=True, training=True, save=True,
             limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None, seed=0, rng=None, per_agent_api=False,
             fused=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
-            learn_steps=5, learn_kinds=None):
+            learn_steps=5, learn_kinds=None, learn_prioritized=None):
     """Extra keyword-only arguments: n_worlds / device / seed / rng / synthetic_agents / refill_below (Environment); per_agent_api=True makes the reference's literal
     per-agent get_action / learn calls; fused (default: True for rng="philox" without per_agent_api) runs the loop through
     Environment.run -- whole chunks of ticks per launch, ending where the Tracker closes an interval -- instead of three launches
@@ -51,7 +51,21 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     brain.soft_update_freq lies in (last - learn_every, last] (D3QN.py:125-126).  The DQN learners' call is a separate launch and draws
     what it draws without D3QN learners.  The same two deviations apply.  learn_steps: an int is the DQN learners' count; a dict by
     method name ({"DQN": 5, "D3QN": 1}) sets it per kind.  A name no entry point trains (PERD3QN, PPO, PERDQN), or learn_kinds without
-    learn="device", is a ValueError before a device is touched."""
+    learn="device", is a ValueError before a device is touched.
+    learn_prioritized (default None: every run is what it was; True needs learn="device" and at least one Models.PERD3QN, ValueError
+    otherwise, before a device is touched; it needs no learn_kinds; the default `learn_every` stays the smallest train_freq of the DQN /
+    D3QN learners -- a PERD3QN's train_freq sets it only where PERD3QN brains are the only learners): every PERD3QN brain trains through rl_learn_prioritized on a
+    prioritised memory beside a ring of brain.capacity rows (10,000, PERD3QN.py:49).  The schedule is the D3QN learners': after an
+    episode `last` that is a multiple of `learn_every` and greater than brain.exploration (PERD3QN.py:120), behind the DQN and D3QN
+    calls (which stay bit for bit what they are without the keyword), one prioritised draw (rl_learn_prioritized_draw: rows appended
+    since the last draw get the priority maximum, PERD3QN.py:147; then 64 draws with probability priority^0.6 / sum, with replacement,
+    PERD3QN.py:157-165) and ONE update (PERD3QNAgent.train(), PERD3QN.py:94-115: the D3QN update on the plain MSE loss -- the reference
+    computes importance weights and never uses them -- then priority = |max_a q'_target(s') - q_eval(s)[a]| for the batch rows); the
+    target is synced iff a multiple of brain.soft_update_freq lies in (last - learn_every, last].  The same two deviations apply: a
+    brain trains once per `learn_every` episodes, so ALL rows appended between two calls get the maximum as of the earlier call (the
+    reference's per-agent train() calls change it in between); draws are by content key.  The run-to-run caveat is sharper here: a ring
+    holds only 10,000 rows and a chunk of 256 worlds appends far more than that, so which rows survive depends on append order --
+    a second identical call repeats bit for bit only while no chunk appends more than the ring holds."""
     if learn == "device" and (per_agent_api or fused is False):
         raise ValueError("trainer(learn='device') needs the fused path (fused=True, per_agent_api=False): the replay rings are filled "
                          "inside the multi-tick launches")
@@ -60,7 +74,8 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
                       interactive_results=visualize_results, google_colab=google_colab, training=training,
                       limit_reproduction=limit_reproduction, incentivize_killing=incentivize_killing, n_worlds=n_worlds,
                       device=device, seed=seed, rng=rng, synthetic_agents=synthetic_agents, refill_below=refill_below, dist=dist,
-                      world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps, learn_kinds=learn_kinds)
+                      world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps, learn_kinds=learn_kinds,
+                      learn_prioritized=learn_prioritized)
     env.reset()
     if fused is None:
         fused = env.rng == "philox" and not per_agent_api

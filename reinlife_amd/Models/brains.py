@@ -5,7 +5,8 @@ batched over all agents through Environment.act(), or one state at a time throug
 
 The per-agent learn() of the reference's brains is accepted and ignored, so that trainer() loops written for the reference keep
 running (a warning is issued once).  DQN brains learn on the device instead, through trainer(learn="device") / learn.DeviceLearner
-(rl_learn), and D3QN brains with learn_kinds=("DQN", "D3QN") (rl_learn_dueling); the other kinds stay frozen.
+(rl_learn), D3QN brains with learn_kinds=("DQN", "D3QN") (rl_learn_dueling) and PERD3QN brains with learn_prioritized=True
+(rl_learn_prioritized, with their prioritised memory); PPO and PERDQN brains stay frozen.
 """
 import random
 import warnings

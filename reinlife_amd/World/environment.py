@@ -158,7 +158,7 @@ class Environment:
                  static_families=True, interactive_results=False, google_colab=False, training=True, save=False,
                  pastel_colors=False, limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None,
                  seed=0, rng=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
-                 learn_steps=5, learn_kinds=None):
+                 learn_steps=5, learn_kinds=None, learn_prioritized=None):
         if not brains:
             raise ValueError("Environment needs a non-empty list of brains")
         if learn not in (None, "device"):
@@ -173,6 +173,15 @@ class Environment:
         if unknown or not self.learn_kinds:
             raise ValueError("learn_kinds: no entry point trains %s brains; the kinds that learn on the device are %s"
                              % (", ".join(map(str, unknown)) or "()", ", ".join(sorted(ENTRY_BY_METHOD))))
+        # learn_prioritized=True: every PERD3QN brain trains through rl_learn_prioritized on a prioritised memory (PERD3QN.py:94-115,
+        # 133-182).  A keyword of its own: learn_kinds and ENTRY_BY_METHOD answer what they answered.  Checked before a device is touched.
+        if learn_prioritized not in (None, True):
+            raise ValueError("learn_prioritized must be None or True, got %r" % (learn_prioritized,))
+        if learn_prioritized and learn != "device":
+            raise ValueError("learn_prioritized=True needs learn='device' (got learn=%r)" % (learn,))
+        if learn_prioritized and not any(getattr(b, "method", None) == "PERD3QN" for b in brains):
+            raise ValueError("learn_prioritized=True needs at least one Models.PERD3QN brain (got %s)" % ", ".join(str(getattr(b, "method", b)) for b in brains))
+        self.learn_prioritized = bool(learn_prioritized)
         # learn_steps: minibatch updates per call -- an int is the DQN learners' (as always), a dict by method name sets it per kind;
         # D3QN defaults to 1 (D3QNAgent.train() makes one update)
         self.learn_steps_of = {"DQN": 5, "D3QN": 1}
@@ -271,20 +280,27 @@ class Environment:
             from ..learn import BUFFER_LIMIT, DeviceLearner, entry_of
             entries = {k: entry_of(b.kind) for k, b in enumerate(brains) if b.method in self.learn_kinds}
             entries = {k: e for k, e in entries.items() if e is not None}
-            if any(e == "rl_learn_dueling" for e in entries.values()):
-                # a D3QN learner's ring holds its brain's `capacity` rows (D3QN.py:62: 10,000); every other ring stays DQN.py:15's
-                self.worlds.enable_capture([int(b.capacity) if entries.get(k) == "rl_learn_dueling" else BUFFER_LIMIT for k, b in enumerate(brains)])
+            prio = [k for k, b in enumerate(brains) if self.learn_prioritized and b.method == "PERD3QN"]
+            if prio or any(e == "rl_learn_dueling" for e in entries.values()):
+                # a D3QN or prioritised PERD3QN learner's ring holds its brain's `capacity` rows (D3QN.py:62, PERD3QN.py:49, 55: 10,000);
+                # every other ring stays DQN.py:15's
+                self.worlds.enable_capture([int(b.capacity) if (entries.get(k) == "rl_learn_dueling" or k in prio) else BUFFER_LIMIT for k, b in enumerate(brains)])
             else:
                 self.worlds.enable_capture(BUFFER_LIMIT)
             for k in entries:
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k])
+            for k in prio:
+                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], prioritized=True)
             if not self.learners:
                 raise ValueError("learn='device': none of the brains is of a kind rl_learn trains (DQN)" if self.learn_kinds == ("DQN",) else
                                  "learn='device': none of the brains is of a kind in learn_kinds %r" % (self.learn_kinds,))
-            self.learn_every = int(learn_every) if learn_every is not None else min(l.train_freq for l in self.learners.values())
+            # the default period is the smallest train_freq of the learners a run has WITHOUT learn_prioritized, so that the keyword does
+            # not move their schedule; the prioritised learners' own train_freq counts only where they are the only learners
+            timed = [l for l in self.learners.values() if l.entry != "rl_learn_prioritized"] or list(self.learners.values())
+            self.learn_every = int(learn_every) if learn_every is not None else min(l.train_freq for l in timed)
             frozen = ["%d (%s)" % (k, b.method) for k, b in enumerate(brains) if k not in self.learners]
             if frozen:
-                warn_inference_only(frozen, self.learn_kinds)
+                warn_inference_only(frozen, self.learn_kinds + (("PERD3QN (prioritised)",) if self.learn_prioritized else ()))
         elif training:
             warn_inference_only()
 
@@ -570,6 +586,7 @@ class Environment:
         frozen = [k for k in range(len(self.brains)) if k not in self.learners]
         dqn = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn")
         duel = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_dueling")
+        prio = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_prioritized")
         note = []
         if dqn:
             note.append("brains %s trained on the device (rl_learn: %d minibatch updates every %d episodes, rows drawn by content key with replacement)"
@@ -578,8 +595,13 @@ class Environment:
             note.append("brains %s trained on the device (rl_learn_dueling: %d minibatch update(s) of batch %s every %d episodes once past the brain's "
                         "exploration, target synced every soft_update_freq episodes, rows drawn by content key with replacement)"
                         % (duel, self.learn_steps_of["D3QN"], sorted({self.learners[k].batch for k in duel}), self.learn_every))
+        if prio:
+            note.append("brains %s trained on the device (rl_learn_prioritized: one minibatch update of batch %s every %d episodes once past the brain's "
+                        "exploration, target synced every soft_update_freq episodes, rows drawn with probability priority^0.6 / sum by content key "
+                        "with replacement; rows appended between two calls get the priority maximum as of the earlier call)"
+                        % (prio, sorted({self.learners[k].batch for k in prio}), self.learn_every))
         if frozen:
-            note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if duel else
+            note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if (duel or prio) else
                         "brains %s as loaded / initialised (their kinds do not learn in this build)" % frozen)
         return "; ".join(note)
 
@@ -589,7 +611,10 @@ class Environment:
         D3QN learners (learn_kinds) train in a call of their own behind it -- the DQN learners' call and draws are what they are without
         them: D3QNAgent.learn's schedule (D3QN.py:118-126) at this build's granularity.  `last` is the episode just finished: a learner
         trains only once last > brain.exploration, and its target is synced in this call iff a multiple of brain.soft_update_freq lies
-        in (last - learn_every, last].  last=None: every D3QN learner trains, sync_target as the learner holds it."""
+        in (last - learn_every, last].  last=None: every D3QN learner trains, sync_target as the learner holds it.
+        Prioritised PERD3QN learners (learn_prioritized=True) follow on the same schedule (PERD3QN.py:117-125 is D3QN.py:118-126), behind
+        the DQN and D3QN calls, which stay what they are without them: one prioritised draw (DeviceWorlds.draw_prioritized, two launches)
+        and one rl_learn_prioritized, ONE update per call as PERD3QNAgent.train() makes."""
         dqn = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn"]
         if dqn:
             self.worlds.learn(dqn, self.learn_steps, slots=self.worlds.draw_slots(dqn, self.learn_steps))
@@ -602,6 +627,14 @@ class Environment:
                 for l in ls:
                     l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
             self.worlds.learn(ls, n, slots=self.worlds.draw_slots(ls, n))
+        prio = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_prioritized"
+                and (last is None or last > self.learners[k].exploration)]
+        for batch in sorted({l.batch for l in prio}):
+            ls = [l for l in prio if l.batch == batch]
+            if last is not None:
+                for l in ls:
+                    l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
+            self.worlds.learn(ls, 1, slots=self.worlds.draw_prioritized(ls, 1))
 
     def sync_learners(self):
         """The trained parameters into the brains' modules (DeviceLearner.sync_to_module): what Saver and state_dict() read."""
@@ -751,7 +784,7 @@ def warn_inference_only(frozen=None, kinds=("DQN",)):
         if tuple(kinds) == ("DQN",):
             warnings.warn("learn='device' trains the DQN brains of this run; brains %s are of kinds rl_learn does not train yet: they stay "
                           "inference only -- brain.learn() is a no-op for them and their weights are NOT updated (D3QN brains learn with "
-                          "learn_kinds=('DQN', 'D3QN'))." % ", ".join(frozen), stacklevel=3)
+                          "learn_kinds=('DQN', 'D3QN'), PERD3QN brains with learn_prioritized=True)." % ", ".join(frozen), stacklevel=3)
         else:
             warnings.warn("learn='device' trains the %s brains of this run; brains %s are of other kinds (or of kinds no entry point trains): they stay "
                           "inference only -- brain.learn() is a no-op for them and their weights are NOT updated." % (" and ".join(kinds), ", ".join(frozen)), stacklevel=3)

@@ -70,7 +70,12 @@ class Learner(C.Structure):  # rl_learner
                 + [(n, C.c_int32) for n in ("batch", "min_size", "sync_target")] + [("loss", C.c_void_p), ("grad", C.c_void_p)])
 
 
+class Prio(C.Structure):  # rl_prio
+    _fields_ = [(n, C.c_void_p) for n in ("priority", "weight", "keys", "prio_max", "seen")] + [("alpha", C.c_float)]
+
+
 SITE_LEARN = 10          # RL_SITE_LEARN: the Philox site of rl_learn's minibatch draws
+SITE_LEARN_PRIO = 11     # RL_SITE_LEARN_PRIO: the Philox site of rl_learn_prioritized_draw's draws
 MAX_CAPTURE_BRAINS = 16  # RL_MAX_CAPTURE_BRAINS
 
 
@@ -114,6 +119,9 @@ ABI = [
     ("rl_learn_dueling_supported", C.c_int, [C.c_int]),
     ("rl_learn_dueling", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, C.POINTER(_P), _P, _P]),
+    ("rl_learn_prioritized_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Prio), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_prioritized_supported", C.c_int, [C.c_int]),
+    ("rl_learn_prioritized", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Prio), C.c_int, C.c_int, _P, _P]),
     ("rl_render", C.c_int, [_P, C.POINTER(RenderStyle), _P, C.c_int, _P, _P]),
     ("rl_set_option", C.c_int, [C.c_char_p, C.c_char_p]),
     ("rl_get_option", C.c_int, [_P, C.c_char_p]),

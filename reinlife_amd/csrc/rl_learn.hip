@@ -363,14 +363,6 @@ struct DrawArgs {
     uint64_t seed;
     int n_steps;
 };
-__device__ inline uint64_t learn_mix64(uint64_t z)   // splitmix64's finalizer
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ inline uint64_t learn_term(int position, uint32_t bits) { return learn_mix64(((uint64_t)(position + 1) << 32) | bits); }
-
 // one wave per ring row: keys[row] = sum of the terms of state (positions 0..152), state_prime (153..305), action, reward, done, age
 __global__ __launch_bounds__(256) void k_learn_keys(const DrawArgs A)
 {
@@ -380,14 +372,7 @@ __global__ __launch_bounds__(256) void k_learn_keys(const DrawArgs A)
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= size) return;
-    uint64_t k = 0;
-    for (int f = lane; f < RL_OBS_DIM; f += 64) {
-        k += learn_term(f, __float_as_uint(B.r_state[(size_t)row * RL_OBS_DIM + f]));
-        k += learn_term(RL_OBS_DIM + f, __float_as_uint(B.r_state_prime[(size_t)row * RL_OBS_DIM + f]));
-    }
-    if (lane == 0) k += learn_term(2 * RL_OBS_DIM, (uint32_t)(uint8_t)B.r_action[row]) + learn_term(2 * RL_OBS_DIM + 1, __float_as_uint(B.r_reward[row]))
-                      + learn_term(2 * RL_OBS_DIM + 2, (uint32_t)B.r_done[row]) + learn_term(2 * RL_OBS_DIM + 3, (uint32_t)B.r_age[row]);
-    for (int o = 32; o > 0; o >>= 1) k += __shfl_xor((unsigned long long)k, o);
+    const uint64_t k = learn_row_key(B.r_state, B.r_state_prime, B.r_action, B.r_reward, B.r_done, B.r_age, row, lane);
     if (lane == 0) B.keys[row] = k;
 }
 

@@ -1,6 +1,6 @@
-// rl_learn_dev.h -- what the learning units (rl_learn.hip: k_learn_dqn, rl_learn_dueling.hip: k_learn_d3qn) share: torch's Adam update
-// of one parameter, the toward-zero f16 split of rl_policy.hip's host packer on the device, the packed layouts' index rule and the
-// decimal a float hyperparameter stands for.  Everything is inline in an unnamed namespace: each unit gets its own copy.
+// rl_learn_dev.h -- what the learning units (rl_learn.hip: k_learn_dqn, rl_learn_dueling.hip: k_learn_d3qn, rl_learn_prio.hip: the prioritised draw) share: torch's Adam update
+// of one parameter, the toward-zero f16 split of rl_policy.hip's host packer on the device, the packed layouts' index rule, the
+// content key of a ring row and the decimal a float hyperparameter stands for.  Everything is inline in an unnamed namespace: each unit gets its own copy.
 #pragma once
 #include "rl_policy_dev.h"
 
@@ -56,6 +56,31 @@ __device__ inline void learn_store_fragment(const float (&x)[8], uint4* hi_dst, 
     *lo_dst = uint4{lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16)};
 }
 __device__ inline int learn_hidden_k(int t, int c, int e, int lane) { const int r = 8 * c + e; return 32 * t + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+
+// ---- the content key of a ring row (rl_learn_draw, rl_learn_prioritized_draw): a sum of mixed (position, bits) terms, so any summation
+// order gives the same key ----
+__device__ inline uint64_t learn_mix64(uint64_t z)   // splitmix64's finalizer
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ inline uint64_t learn_term(int position, uint32_t bits) { return learn_mix64(((uint64_t)(position + 1) << 32) | bits); }
+// by one whole wave (lane 0..63): the terms of state (positions 0..152), state_prime (153..305), action, reward, done, age; every lane
+// returns the key
+__device__ inline uint64_t learn_row_key(const float* r_state, const float* r_state_prime, const int8_t* r_action, const float* r_reward,
+                                         const uint8_t* r_done, const int32_t* r_age, long long row, int lane)
+{
+    uint64_t k = 0;
+    for (int f = lane; f < RL_OBS_DIM; f += 64) {
+        k += learn_term(f, __float_as_uint(r_state[(size_t)row * RL_OBS_DIM + f]));
+        k += learn_term(RL_OBS_DIM + f, __float_as_uint(r_state_prime[(size_t)row * RL_OBS_DIM + f]));
+    }
+    if (lane == 0) k += learn_term(2 * RL_OBS_DIM, (uint32_t)(uint8_t)r_action[row]) + learn_term(2 * RL_OBS_DIM + 1, __float_as_uint(r_reward[row]))
+                      + learn_term(2 * RL_OBS_DIM + 2, (uint32_t)r_done[row]) + learn_term(2 * RL_OBS_DIM + 3, (uint32_t)r_age[row]);
+    for (int o = 32; o > 0; o >>= 1) k += __shfl_xor((unsigned long long)k, o);
+    return k;
+}
 
 // The decimal a float hyperparameter stands for (0.999f -> 0.999, not 0.99900001287): torch computes Adam's bias corrections from the
 // Python doubles, and 1 - 0.999f^t differs from 1 - 0.999^t by 1.3e-5 of itself at t = 1.

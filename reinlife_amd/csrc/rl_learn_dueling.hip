@@ -34,6 +34,14 @@
 // The gradients of the two heads (1,161 parameters) are summed before da / dv overwrite HA / HV and held in registers (at most three
 // per thread) until their Adam update.  All back-propagated rows are complete before the first parameter changes.
 //
+// Prioritised memory (k_learn_d3qn<true>, rl_learn_prioritized).  PERD3QNAgent.train() (PERD3QN.py:94-115) is this update with one
+// addition: the loss is the same plain nn.MSELoss (PERD3QN.py:56, 109 -- sample()'s importance weights are computed and never used), and
+// after the forward passes every batch row's priority becomes |max_a q'_target(s') - q_eval(s)[a]| (PERD3QN.py:110-111: the reference's
+// expression, not the TD error).  The thread that forms a row's td writes priority[slot] from the same two numbers; duplicated slots write
+// equal bits.  After the last step of a call that trained the workgroup leaves max(priority[0 .. size)) in *prio_max: what store() gives
+// the next new rows (PERD3QN.py:147).  The maximum is over the rows as they stand: the caller has drawn (and so stamped the new rows)
+// since the last append -- the order rl_learn_prioritized_draw, rl_learn_prioritized that the slots argument asks for anyway.  The arithmetic of the update is the D3QN instantiation's, instruction for instruction.
+//
 // Packing.  After the last step the workgroup rewrites `packed` from the final parameters: rl_policy.hip's pack_in_layer,
 // pack_hidden_layer x 2, pack_head 128 -> 8 and pack_head 128 -> 1 at Layout.l1 / l2a / ha / l2b / hb, bit for bit.
 #include "rl_learn_dev.h"
@@ -70,8 +78,14 @@ struct DuelBrain {
     int batch, min_size, sync_target;
 };
 
+struct DuelPrio {                // the prioritised memory of a brain (k_learn_d3qn<true> only)
+    float* priority;             // [ring capacity]
+    float* prio_max;             // [1]
+};
+
 struct DuelArgs {
     DuelBrain b[RL_MAX_CAPTURE_BRAINS];
+    DuelPrio p[RL_MAX_CAPTURE_BRAINS];
     const int32_t* slots;        // [n_learners][n_steps][batch] or null
     int32_t* err;
     uint64_t seed;
@@ -326,6 +340,7 @@ __device__ __forceinline__ void duel_pack(const float* P, float* packed, float* 
     duel_pack_head(P + oWv2, P + oBv2, 1, sc + 392, un + 392, packed + L.hb, tid);
 }
 
+template <bool PRIO>
 __global__ __launch_bounds__(kDBlock) void k_learn_d3qn(const DuelArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) float duel_lds[];
@@ -418,8 +433,10 @@ __global__ __launch_bounds__(kDBlock) void k_learn_d3qn(const DuelArgs A)
         __syncthreads();
         if (tid < kDRows) {
             const float y = row_r[tid] + (B.gamma * row_mask[tid]) * row_y[tid];
-            const float td = ((adv[tid * 8 + row_a[tid]] + val[tid]) - batch_mean) - y;
+            const float q = (adv[tid * 8 + row_a[tid]] + val[tid]) - batch_mean;
+            const float td = q - y;
             const bool in = tid < batch;
+            if (PRIO && in) A.p[brain].priority[row_slot[tid]] = fabsf(row_y[tid] - q);   // PERD3QN.py:110, from this step's pre-update parameters
             row_y[tid] = in ? td * td : 0.0f;
             row_g[tid] = in ? (2.0f * td) * inv_batch : 0.0f;
         }
@@ -523,6 +540,20 @@ __global__ __launch_bounds__(kDBlock) void k_learn_d3qn(const DuelArgs A)
     if (B.sync_target)     // D3QN.py:125-126, on the caller's schedule
         for (int i = tid; i < kNParams; i += kDBlock) B.target[i] = B.params[i];
     if (tid == 0) { B.state[0] = steps_taken; B.state[1] = calls + 1; }
+    if (PRIO && train && size > 0) {   // *prio_max = max(priority[0 .. size)) after a call that trained (a call below the size gate wrote no
+                                       // priority and leaves the maximum alone): fmaxf is exact, so the order of the reduction does not matter
+        const float* pr = A.p[brain].priority;
+        float mx = 0.0f;      // (priorities are |.|: never below zero)
+        for (long long i = tid; i < size; i += kDBlock) mx = fmaxf(mx, pr[i]);
+        wt[tid] = mx;
+        __syncthreads();
+        for (int o = kDBlock / 2; o > 0; o >>= 1) {
+            if (tid < o) wt[tid] = fmaxf(wt[tid], wt[tid + o]);
+            __syncthreads();
+        }
+        if (tid == 0) *A.p[brain].prio_max = wt[0];
+        __syncthreads();      // the packer's scales take the tile next
+    }
     duel_pack(B.params, B.packed, wt, wt + kNFeat, tid);
 }
 
@@ -530,8 +561,9 @@ __global__ __launch_bounds__(kDBlock) void k_learn_d3qn(const DuelArgs A)
 
 int rl_learn_dueling_supported_impl(int kind) { return kind == RL_D3QN ? 1 : 0; }
 
-int rl_learn_dueling_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, const int32_t* slots,
-                            hipStream_t stream)
+template <bool PRIO>
+static int duel_launch(const char* who, rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners, int n_steps,
+                       const int32_t* slots, hipStream_t stream)
 {
     DuelArgs a{};
     for (int i = 0; i < n_learners; ++i) {
@@ -545,14 +577,29 @@ int rl_learn_dueling_launch(rl_world* h, const rl_learner* learners, const rl_re
         b.lr = learn_decimal(l.lr); b.beta1 = learn_decimal(l.beta1); b.beta2 = learn_decimal(l.beta2);
         b.gamma = l.gamma; b.eps = l.eps; b.w1 = (float)(1.0 - b.beta1); b.w2 = (float)(1.0 - b.beta2);
         b.batch = l.batch; b.min_size = l.min_size; b.sync_target = l.sync_target;
+        if (PRIO) { a.p[i].priority = prios[i].priority; a.p[i].prio_max = prios[i].prio_max; }
     }
     a.slots = slots; a.err = h->err_flag; a.seed = h->cfg.seed; a.n_steps = n_steps;
     {   // the large dynamic-LDS window (158 KB): asked for at every call -- idempotent, host-only, and right on whatever device is current
-        const hipError_t e = hipFuncSetAttribute((const void*)k_learn_d3qn, hipFuncAttributeMaxDynamicSharedMemorySize, kDLdsBytes);
-        if (e != hipSuccess) { rl_set_error("rl_learn_dueling: hipFuncSetAttribute(%d bytes of LDS) failed: %s", kDLdsBytes, hipGetErrorString(e)); return RL_E_LAUNCH; }
+        const hipError_t e = hipFuncSetAttribute((const void*)k_learn_d3qn<PRIO>, hipFuncAttributeMaxDynamicSharedMemorySize, kDLdsBytes);
+        if (e != hipSuccess) { rl_set_error("%s: hipFuncSetAttribute(%d bytes of LDS) failed: %s", who, kDLdsBytes, hipGetErrorString(e)); return RL_E_LAUNCH; }
     }
-    hipLaunchKernelGGL(k_learn_d3qn, dim3(n_learners), dim3(kDBlock), kDLdsBytes, stream, a);
+    hipLaunchKernelGGL(k_learn_d3qn<PRIO>, dim3(n_learners), dim3(kDBlock), kDLdsBytes, stream, a);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rl_set_error("rl_learn_dueling: kernel launch failed: %s", hipGetErrorString(e)); return RL_E_LAUNCH; }
+    if (e != hipSuccess) { rl_set_error("%s: kernel launch failed: %s", who, hipGetErrorString(e)); return RL_E_LAUNCH; }
     return RL_OK;
+}
+
+int rl_learn_dueling_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, const int32_t* slots,
+                            hipStream_t stream)
+{
+    return duel_launch<false>("rl_learn_dueling", h, learners, rings, nullptr, n_learners, n_steps, slots, stream);
+}
+
+int rl_learn_prioritized_supported_impl(int kind) { return kind == RL_PERD3QN ? 1 : 0; }
+
+int rl_learn_prioritized_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners, int n_steps,
+                                const int32_t* slots, hipStream_t stream)
+{
+    return duel_launch<true>("rl_learn_prioritized", h, learners, rings, prios, n_learners, n_steps, slots, stream);
 }

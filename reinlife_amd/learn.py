@@ -1,4 +1,5 @@
-"""DeviceLearner: what a DQN or D3QN brain needs to learn on the device (rl_learn / rl_learn_dueling, include/reinlife_hip.h) -- the flat f32 master parameters,
+"""DeviceLearner: what a DQN, D3QN or (prioritized=True) PERD3QN brain needs to learn on the device (rl_learn / rl_learn_dueling /
+rl_learn_prioritized, include/reinlife_hip.h; PPO and PERDQN brains stay frozen) -- the flat f32 master parameters,
 the target network, Adam's moments, the step / call counters and the packed weights the acting kernels read, all as device tensors.
 
 Reference: DQNAgent owns `agent`, `target`, `memory` and `optimizer` (ReinLife/Models/DQN.py:48-52); train() (DQN.py:80-83, 142-153)
@@ -10,7 +11,16 @@ calls is the caller's (Environment: once per `learn_every` episodes), not "whene
 D3QNAgent owns `eval_net`, `target_net`, `buffer` and `optimizer` (ReinLife/Models/D3QN.py:58-62); train() (D3QN.py:97-116) samples ONE
 minibatch of 64 and makes one Adam step on its MSE loss; learn() (D3QN.py:118-126) trains only once n_epi > exploration and copies eval ->
 target every soft_update_freq episodes.  The learner takes lr, gamma, batch, train_freq, exploration and soft_update_freq from the
-brain; its only size gate is random.sample's need of `batch` rows (min_size = batch - 1); the same two deviations apply."""
+brain; its only size gate is random.sample's need of `batch` rows (min_size = batch - 1); the same two deviations apply.
+
+PERD3QNAgent (ReinLife/Models/PERD3QN.py:48-66) is the D3QN agent with a prioritised memory: train() (PERD3QN.py:94-115) makes the same
+update on the same plain MSE loss -- sample()'s importance weights are computed and never used -- and then sets the priority of every
+batch row to |max_a q'_target(s') - q_eval(s)[a]| (PERD3QN.py:110-111).  DeviceLearner(brain, device, ring, prioritized=True) is that
+agent's learner (rl_learn_prioritized): besides the D3QN learner's tensors it owns the memory's priorities (one per ring row), their
+maximum, the ring count as of the last draw, and two scratch columns of the draw (DeviceWorlds.draw_prioritized: probability
+priority^0.6 / sum, with replacement, by content key).  Its only size gate is np.random.choice's need of one row (min_size = 0).  The
+same two deviations apply, and one more follows from the first: every row appended between two learning calls gets the priority
+maximum as of the earlier call."""
 import copy
 import ctypes as C
 
@@ -30,9 +40,14 @@ def entry_of(kind):
 
 
 class DeviceLearner:
-    def __init__(self, brain, device="cuda:0", ring=None):
+    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False):
         lib = _lib.lib()
-        self.entry = entry_of(brain.kind)
+        if prioritized:   # an explicit opt-in: entry_of() and ENTRY_BY_METHOD keep answering what they answered
+            if not lib.rl_learn_prioritized_supported(brain.kind):
+                raise ValueError("prioritized=True is for PERD3QN brains (rl_learn_prioritized); got a %s brain (kind %d)" % (brain.method, brain.kind))
+            self.entry = "rl_learn_prioritized"
+        else:
+            self.entry = entry_of(brain.kind)
         if self.entry is None:
             raise ValueError("no entry point trains %s brains (kind %d): only DQN (rl_learn) and D3QN (rl_learn_dueling) learn on the device"
                              % (brain.method, brain.kind))
@@ -55,12 +70,17 @@ class DeviceLearner:
         else:   # D3QN.py:54-72: the brain's own hyperparameters
             self.lr = float(getattr(brain, "learning_rate", 1e-3))
             self.gamma, self.batch = float(getattr(brain, "gamma", 0.99)), int(getattr(brain, "batch_size", 64))
-            self.min_size = self.batch - 1                       # random.sample needs `batch` rows (D3QN.py:98, 140): the only gate
+            # random.sample needs `batch` rows (D3QN.py:98, 140): the only gate; np.random.choice (PERD3QN.py:165) needs one
+            self.min_size = 0 if prioritized else self.batch - 1
             self.exploration, self.soft_update_freq = int(getattr(brain, "exploration", 1000)), int(getattr(brain, "soft_update_freq", 200))
             self.n_steps_default = 1                             # D3QNAgent.train() makes one update
             self.sync_target = False                             # the schedule's (D3QN.py:125-126, Environment.learn_now)
         self.beta1, self.beta2, self.eps = 0.9, 0.999, 1e-8      # torch.optim.Adam's defaults (DQN.py:52, D3QN.py:61)
         self.ring = ring          # the brain's replay ring: a dict of device tensors as DeviceWorlds.enable_capture() makes them
+        self.alpha = 0.6          # PERD3QN.py:134
+        self.priority = self.weight = self.keys = self.prio_max = self.seen = None
+        if prioritized and ring is not None:
+            self._make_prio()
         self.loss = None          # optional device float32 [n_steps]
         self.grad = None          # optional device float32 [n_steps, n_params] (tests, diagnostics)
 
@@ -78,6 +98,25 @@ class DeviceLearner:
         return _lib.Replay(*[p(r.get(n)) for n in ("state", "state_prime", "action", "reward", "done", "prob", "age", "count")],
                            int(r["state"].shape[0]))
 
+    def _make_prio(self):
+        """The prioritised memory beside the ring (rl_prio), sized to it: no priorities yet, maximum 1.0 (PERD3QN.py:147), nothing seen."""
+        capacity = int(self.ring["state"].shape[0])
+        self.priority = torch.zeros(capacity, dtype=torch.float32, device=self.device)
+        self.weight = torch.zeros(capacity, dtype=torch.float32, device=self.device)
+        self.keys = torch.zeros(capacity, dtype=torch.int64, device=self.device)
+        self.prio_max = torch.ones(1, dtype=torch.float32, device=self.device)
+        self.seen = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def prio_struct(self):
+        if self.entry != "rl_learn_prioritized":
+            raise _lib.ReinLifeHipError("this DeviceLearner has no prioritised memory (DeviceLearner(..., prioritized=True))")
+        if self.ring is None:
+            raise _lib.ReinLifeHipError("this DeviceLearner has no replay ring (DeviceLearner.ring)")
+        if self.priority is None or self.priority.numel() != self.ring["state"].shape[0]:
+            self._make_prio()
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        return _lib.Prio(p(self.priority), p(self.weight), p(self.keys), p(self.prio_max), p(self.seen), self.alpha)
+
     @property
     def steps(self):
         """Adam steps taken so far (reads the device counter: synchronises)."""
@@ -94,8 +133,8 @@ class DeviceLearner:
 
     def sync_to_module(self):
         """The trained parameters into brain.agent and the target network's into brain.target (made on first use: a copy, no
-        generator draw), so that Saver and state_dict() see them.  D3QN: into brain.eval_net and brain.target_net."""
-        if self.entry == "rl_learn_dueling":
+        generator draw), so that Saver and state_dict() see them.  D3QN and PERD3QN: into brain.eval_net and brain.target_net."""
+        if self.entry in ("rl_learn_dueling", "rl_learn_prioritized"):
             self._load(self.brain.eval_net, self.params.cpu().numpy())
             self._load(self.brain.target_net, self.target.cpu().numpy())
             return

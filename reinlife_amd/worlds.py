@@ -444,6 +444,28 @@ class DeviceWorlds:
         self.launches += 2
         return slots
 
+    def draw_prioritized(self, learners, n_steps):
+        """The minibatches of prioritised learners (DeviceLearner(..., prioritized=True)) for learn(learners, n_steps, slots=...):
+        PrioritizedReplayBuffer.sample's draw (PERD3QN.py:157-165) on the device (rl_learn_prioritized_draw) -- first every row appended
+        since the last draw gets the priority maximum (store(), PERD3QN.py:147-153), then each draw takes a row with probability
+        priority^alpha / sum, with replacement, by a key of the rows' content: the same rows whatever slots they sit in.  All n_steps
+        are drawn from the priorities as they stand now.  Device int32 [len(learners), n_steps, batch], queued on the current stream."""
+        n = len(learners)
+        if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
+            raise ValueError("draw_prioritized(): 1 to %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
+        if len({l.batch for l in learners}) != 1:
+            raise ValueError("draw_prioritized(): the learners of a call must share one batch size")
+        if any(l.entry != "rl_learn_prioritized" for l in learners):
+            raise ValueError("draw_prioritized(): every learner must be a prioritised one (DeviceLearner(..., prioritized=True))")
+        arr = (_lib.Learner * n)(*[l.struct() for l in learners])
+        rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
+        prios = (_lib.Prio * n)(*[l.prio_struct() for l in learners])
+        slots = torch.zeros((n, int(n_steps), int(learners[0].batch)), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.rl_learn_prioritized_draw(self.handle, arr, rings, prios, n, int(n_steps), _ptr(slots), self._stream()),
+                   "rl_learn_prioritized_draw")
+        self.launches += 2
+        return slots
+
     def learn(self, learners, n_steps, slots=None):
         """DQNAgent.train() (DQN.py:80-83, 142-153) for every DeviceLearner of `learners` in ONE launch (rl_learn), queued on the current
         stream behind the ticks launched so far: `n_steps` minibatch updates per brain on its replay ring (learner.ring), then the
@@ -452,7 +474,9 @@ class DeviceWorlds:
         None = drawn on the device, uniformly WITH replacement (learn.philox_slots gives the same numbers on the host; the
         brain index of the draw is the learner's position in `learners`).
         A list of D3QN learners goes to rl_learn_dueling instead (D3QNAgent.train(), D3QN.py:97-116: batch up to 64, MSE, the target copy
-        only when learner.sync_target says so).  The learners of one call must all belong to one entry point: ValueError otherwise."""
+        only when learner.sync_target says so), a list of prioritised PERD3QN learners to rl_learn_prioritized (PERD3QNAgent.train(),
+        PERD3QN.py:94-115: the same update, and the batch rows' priorities rewritten; `slots` must come from draw_prioritized()).  The
+        learners of one call must all belong to one entry point: ValueError otherwise."""
         if not learners:
             return
         n = len(learners)
@@ -470,7 +494,11 @@ class DeviceWorlds:
             slots = slots.to(device=self.device, dtype=torch.int32).contiguous()
             if slots.numel() != n * n_steps * learners[0].batch or len({l.batch for l in learners}) != 1:
                 raise ValueError("learn(): slots must hold [n_learners, n_steps, batch] = [%d, %d, %d] entries" % (n, n_steps, learners[0].batch))
-        _lib.check(getattr(self.lib, entry)(self.handle, arr, rings, n, int(n_steps), _ptr(slots), self._stream()), entry)
+        if entry == "rl_learn_prioritized":
+            prios = (_lib.Prio * n)(*[l.prio_struct() for l in learners])
+            _lib.check(self.lib.rl_learn_prioritized(self.handle, arr, rings, prios, n, int(n_steps), _ptr(slots), self._stream()), entry)
+        else:
+            _lib.check(getattr(self.lib, entry)(self.handle, arr, rings, n, int(n_steps), _ptr(slots), self._stream()), entry)
         self._learn_keep = slots   # (the launch reads the table asynchronously)
         self.launches += 1
 
