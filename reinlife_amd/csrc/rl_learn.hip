@@ -46,8 +46,8 @@ struct LearnBrain {
     const uint8_t* r_done;
     const unsigned long long* r_count;
     long long r_capacity;
-    double lr, beta1, beta2;     // the decimal values the caller's floats stand for (learn_decimal)
-    float gamma, eps, w1, w2;    // w1 = (float)(1 - beta1), w2 = (float)(1 - beta2)
+    double lr, beta1, beta2, eps_d;   // the decimal values the caller's floats stand for (learn_decimal)
+    float gamma;
     int batch, min_size, sync_target;
 };
 
@@ -309,9 +309,9 @@ __global__ __launch_bounds__(kLearnBlock) void k_learn_dqn(const LearnArgs A)
         AdamStep ad;
         ad.p = B.params; ad.m = B.adam_m; ad.v = B.adam_v;
         ad.grad = B.grad ? B.grad + (size_t)s * kNParams : nullptr;
-        ad.w1 = B.w1; ad.w2 = B.w2; ad.beta2 = (float)B.beta2; ad.eps = B.eps;
-        ad.bc2_sqrt = (float)sqrt(1.0 - pow(B.beta2, t));
-        ad.neg_step = (float)(-(B.lr / (1.0 - pow(B.beta1, t))));
+        ad.w1 = 1.0 - B.beta1; ad.w2 = 1.0 - B.beta2; ad.beta2 = B.beta2; ad.eps = B.eps_d;
+        ad.bc2_sqrt = sqrt(1.0 - pow(B.beta2, t));
+        ad.neg_step = -(B.lr / (1.0 - pow(B.beta1, t)));
         learn_wgrad<153, 128, kH1S, kXS>(ad, oW1, d1, xs, tid);
         learn_bgrad<128, kH1S>(ad, oB1, d1, tid);
         learn_wgrad<128, 64, kH2S, kH1S>(ad, oW2, d2, h1, tid);
@@ -428,7 +428,7 @@ int rl_learn_launch(rl_world* h, const rl_learner* learners, const rl_replay* ri
         b.r_state = r.state; b.r_state_prime = r.state_prime; b.r_reward = r.reward; b.r_action = r.action; b.r_done = r.done;
         b.r_count = r.count; b.r_capacity = r.capacity;
         b.lr = learn_decimal(l.lr); b.beta1 = learn_decimal(l.beta1); b.beta2 = learn_decimal(l.beta2);
-        b.gamma = l.gamma; b.eps = l.eps; b.w1 = (float)(1.0 - b.beta1); b.w2 = (float)(1.0 - b.beta2);
+        b.gamma = l.gamma; b.eps_d = learn_decimal(l.eps);
         b.batch = l.batch; b.min_size = l.min_size; b.sync_target = l.sync_target;
     }
     a.slots = slots; a.err = h->err_flag; a.seed = h->cfg.seed; a.n_steps = n_steps;

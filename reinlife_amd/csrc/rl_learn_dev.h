@@ -11,19 +11,24 @@ namespace {
 
 struct AdamStep {
     float *p, *m, *v, *grad;   // grad: this step's row of the caller's buffer or null
-    float w1, w2, beta2, bc2_sqrt, eps, neg_step;
+    double w1, w2, beta2, bc2_sqrt, eps, neg_step;
 };
 // torch.optim.Adam's single-tensor update: exp_avg.lerp_(g, 1 - b1); exp_avg_sq.mul_(b2).addcmul_(g, g, value = 1 - b2);
 // denom = exp_avg_sq.sqrt() / sqrt(1 - b2^t) + eps; param.addcdiv_(exp_avg, denom, value = -lr / (1 - b1^t))
+// The arithmetic of one parameter is double and each of p, m, v is rounded to float ONCE: moments of a run that is under way make
+// m / sqrt(v) reach thousands (a step of thousands of lr) and let m + w1 (g - m) cancel, where float roundings of the intermediate values
+// are no longer small against 1e-5 lr or an ulp of the result (tests/test_hip_learn_edges.py, Adam at step 10,000).  The decimal
+// hyperparameters stay double throughout.
 __device__ inline void adam_update(const AdamStep& a, int idx, float g)
 {
     if (a.grad) a.grad[idx] = g;
-    float m = a.m[idx], v = a.v[idx];
-    m = m + a.w1 * (g - m);
-    v = v * a.beta2 + (a.w2 * g) * g;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    a.m[idx] = m; a.v[idx] = v;
-    a.p[idx] = a.p[idx] + (a.neg_step * m) / denom;
+    const double gd = (double)g;
+    double m = (double)a.m[idx], v = (double)a.v[idx];
+    m = m + a.w1 * (gd - m);
+    v = v * a.beta2 + (a.w2 * gd) * gd;
+    const double denom = sqrt(v) / a.bc2_sqrt + a.eps;
+    a.m[idx] = (float)m; a.v[idx] = (float)v;
+    a.p[idx] = (float)((double)a.p[idx] + (a.neg_step * m) / denom);
 }
 
 // ---- the toward-zero f16 split of rl_policy.hip's host packer (f16_rtz, f16_to_float, split2_host), on the device ----

@@ -73,8 +73,8 @@ struct DuelBrain {
     const uint8_t* r_done;
     const unsigned long long* r_count;
     long long r_capacity;
-    double lr, beta1, beta2;     // the decimal values the caller's floats stand for (learn_decimal)
-    float gamma, eps, w1, w2;    // w1 = (float)(1 - beta1), w2 = (float)(1 - beta2)
+    double lr, beta1, beta2, eps_d;   // the decimal values the caller's floats stand for (learn_decimal)
+    float gamma;
     int batch, min_size, sync_target;
 };
 
@@ -516,9 +516,9 @@ __global__ __launch_bounds__(kDBlock) void k_learn_d3qn(const DuelArgs A)
         AdamStep ad;
         ad.p = P; ad.m = AM; ad.v = AV;
         ad.grad = GR ? GR + (size_t)s * kNParams : nullptr;
-        ad.w1 = B.w1; ad.w2 = B.w2; ad.beta2 = (float)B.beta2; ad.eps = B.eps;
-        ad.bc2_sqrt = (float)sqrt(1.0 - pow(B.beta2, t));
-        ad.neg_step = (float)(-(B.lr / (1.0 - pow(B.beta1, t))));
+        ad.w1 = 1.0 - B.beta1; ad.w2 = 1.0 - B.beta2; ad.beta2 = B.beta2; ad.eps = B.eps_d;
+        ad.bc2_sqrt = sqrt(1.0 - pow(B.beta2, t));
+        ad.neg_step = -(B.lr / (1.0 - pow(B.beta1, t)));
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
             const int idx = tid + kDBlock * p;
@@ -575,7 +575,7 @@ static int duel_launch(const char* who, rl_world* h, const rl_learner* learners,
         b.r_state = r.state; b.r_state_prime = r.state_prime; b.r_reward = r.reward; b.r_action = r.action; b.r_done = r.done;
         b.r_count = r.count; b.r_capacity = r.capacity;
         b.lr = learn_decimal(l.lr); b.beta1 = learn_decimal(l.beta1); b.beta2 = learn_decimal(l.beta2);
-        b.gamma = l.gamma; b.eps = l.eps; b.w1 = (float)(1.0 - b.beta1); b.w2 = (float)(1.0 - b.beta2);
+        b.gamma = l.gamma; b.eps_d = learn_decimal(l.eps);
         b.batch = l.batch; b.min_size = l.min_size; b.sync_target = l.sync_target;
         if (PRIO) { a.p[i].priority = prios[i].priority; a.p[i].prio_max = prios[i].prio_max; }
     }

@@ -65,10 +65,10 @@ def dqn_loss(net, tgt, ring, slots, gamma, dtype):
     return torch.nn.functional.smooth_l1_loss(td, torch.zeros_like(td))
 
 
-def grads64(flat, target_flat, ring, slots, gamma):
-    """(loss, the six gradient tensors) of one minibatch in float64 autograd."""
-    net, tgt = qnet(np.asarray(flat, np.float64)), qnet(np.asarray(target_flat, np.float64))
-    loss = dqn_loss(net, tgt, ring, slots, gamma, torch.float64)
+def grads64(flat, target_flat, ring, slots, gamma, dtype=torch.float64):
+    """(loss, the six gradient tensors) of one minibatch in float64 autograd (dtype=torch.float32: what torch itself makes of it)."""
+    net, tgt = qnet(np.asarray(flat, np.float64), dtype), qnet(np.asarray(target_flat, np.float64), dtype)
+    loss = dqn_loss(net, tgt, ring, slots, gamma, dtype)
     g = torch.autograd.grad(loss, list(net.parameters()))
     return float(loss.detach()), [x.numpy() for x in g]
 
@@ -79,3 +79,53 @@ def adam64(p, m, v, g, t, lr, b1=0.9, b2=0.999, eps=1e-8):
     v = v * b2 + (1 - b2) * g * g
     denom = np.sqrt(v) / np.sqrt(1 - b2 ** t) + eps
     return p - (lr / (1 - b1 ** t)) * m / denom, m, v
+
+
+# ---- inputs beyond the fixtures (tests/test_learn_edges_cpu.py, tests/test_hip_learn_edges.py) ----
+RING_KEYS = ("ring_state", "ring_state_prime", "ring_action", "ring_reward", "ring_done")
+TARGET_SCALE = np.float32(0.96875)   # trained eval weights times this are the target network of the trained-weight cases: q' differs from q
+_pretrained = None
+_edge_rows = {}
+
+
+def pretrained(method):
+    """The reference's trained weights of `method` ("DQN", "D3QN", "PERD3QN"; tests/golden/pretrained.npz) as the eval network, and the
+    same weights times float32(0.96875) as the target -> (eval, target), flat float32."""
+    global _pretrained
+    if _pretrained is None:
+        with np.load(os.path.join(ROOT, "tests", "golden", "pretrained.npz")) as z:
+            _pretrained = {k: z[k] for k in z.files if k.endswith("_weights")}
+        for v in _pretrained.values():
+            v.setflags(write=False)
+    w = _pretrained[method + "_weights"]
+    return w, (w * TARGET_SCALE).astype(np.float32)
+
+
+def edge_ring_rows(n, seed=11):
+    """n seeded ring rows as the worlds write them: observation planes from {0, +-0.5, +-1} (about 15 % non-zero), actions 0..7, rewards
+    from {0, 0.05, 0.3, -1, 5, -10, 400}, about 20 % done, and ages 0..199 ("ring_age", int32).  Generated once per (n, seed), read-only."""
+    if (n, seed) not in _edge_rows:
+        rng = np.random.RandomState(seed)
+
+        def rows():
+            x = (rng.random_sample((n, 153)) < 0.15) * rng.choice(np.array([1.0, -1.0, 0.5, -0.5], np.float32), size=(n, 153))
+            return x.astype(np.float32)
+        r = {"ring_state": rows(), "ring_state_prime": rows(), "ring_action": rng.randint(0, 8, size=n).astype(np.int8),
+             "ring_reward": rng.choice(np.array([0, 0.05, 0.3, -1, 5, -10, 400], np.float32), size=n),
+             "ring_done": (rng.random_sample(n) < 0.2).astype(np.uint8), "ring_age": rng.randint(0, 200, size=n).astype(np.int32)}
+        for v in r.values():
+            v.setflags(write=False)
+        _edge_rows[(n, seed)] = r
+    return _edge_rows[(n, seed)]
+
+
+def relocated(rows, capacity, at):
+    """A ring of `capacity` rows, all zero but for `rows` at slots at .. at + len(rows) - 1."""
+    n = rows["ring_state"].shape[0]
+    assert 0 <= at and at + n <= capacity
+    out = {}
+    for k in RING_KEYS:
+        a = np.zeros((capacity,) + rows[k].shape[1:], rows[k].dtype)
+        a[at:at + n] = rows[k]
+        out[k] = a
+    return out

@@ -113,3 +113,22 @@ def adam64(p, m, v, g, t, lr, b1=0.9, b2=0.999, eps=1e-8):
     v = v * b2 + (1 - b2) * g * g
     denom = np.sqrt(v) / np.sqrt(1 - b2 ** t) + eps
     return p - (lr / (1 - b1 ** t)) * m / denom, m, v
+
+
+def adam32(p, m, v, g, t, lr):
+    """torch.optim.Adam's update made of float32 operations, in numpy, from bias corrections made in double -> (p, m, v): what float32
+    itself makes of a step (the kernels' adam_update takes double arithmetic and rounds p, m and v once)."""
+    f = np.float32
+    p, m, v, g = (np.asarray(x, f) for x in (p, m, v, g))
+    w1, w2, b2 = f(1.0 - 0.9), f(1.0 - 0.999), f(0.999)
+    bc2, neg = f(np.sqrt(1.0 - 0.999 ** t)), f(-(lr / (1.0 - 0.9 ** t)))
+    m2 = m + w1 * (g - m)
+    v2 = v * b2 + (w2 * g) * g
+    return p + (neg * m2) / (np.sqrt(v2) / bc2 + f(1e-8)), m2, v2
+
+
+def adam_moments(n, seed=7):
+    """Moments of a run that is under way: adam_m ~ N(0, 1e-3), adam_v the squares of another N(0, 1e-3) draw -> (m, v), float32."""
+    rng = np.random.RandomState(seed)
+    m = rng.normal(0, 1e-3, n).astype(np.float32)
+    return m, (rng.normal(0, 1e-3, n) ** 2).astype(np.float32)

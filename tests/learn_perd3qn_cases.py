@@ -108,8 +108,9 @@ def _term(position, bits):
     return _mix64((np.uint64(position + 1) << np.uint64(32)) | np.asarray(bits, np.uint64))
 
 
-def content_keys(ring, n):
-    """The 64-bit content keys of the first n fixture rows (age 0), as learn_row_key sums them."""
+def content_keys(ring, n, age=None):
+    """The 64-bit content keys of the first n rows, as learn_row_key sums them; age: the rows' int32 ages (None: age 0)."""
+    age = np.zeros(n, np.int32) if age is None else np.ascontiguousarray(np.asarray(age)[:n], np.int32)
     k = np.zeros(n, np.uint64)
     s, sp = np.ascontiguousarray(ring["ring_state"][:n]).view(np.uint32), np.ascontiguousarray(ring["ring_state_prime"][:n]).view(np.uint32)
     with np.errstate(over="ignore"):
@@ -119,7 +120,7 @@ def content_keys(ring, n):
         k += _term(306, ring["ring_action"][:n].astype(np.uint8))
         k += _term(307, np.ascontiguousarray(ring["ring_reward"][:n]).view(np.uint32))
         k += _term(308, ring["ring_done"][:n])
-        k += _term(309, np.zeros(n, np.uint32))
+        k += _term(309, age.view(np.uint32))
     return k
 
 
@@ -139,3 +140,54 @@ def host_draw(keys, priority, seed, brain, calls, n_draws, alpha=0.6):
             t = np.where(w > 0, -np.log(u) / w, np.inf).astype(np.float32)
         rows[d] = np.lexsort((np.arange(len(keys)), v, t))[0]
     return rows
+
+
+def _salts(seed, brain, calls, site, n_draws):
+    """salt_d = words 0-1 of rl_philox(seed, 0, brain, calls, site, d), d = 0 .. n_draws - 1 -> uint64 [n_draws]."""
+    import ctypes as C
+    from reinlife_amd import _lib
+    lib = _lib.lib()
+    out = (C.c_uint32 * 4)()
+    salts = np.zeros(n_draws, np.uint64)
+    for d in range(n_draws):
+        lib.rl_philox(seed, 0, brain, calls & 0xffffffff, site, d, C.byref(out))
+        salts[d] = (int(out[1]) << 32) | int(out[0])
+    return salts
+
+
+def host_uniform_draw(keys, seed, brain, calls, n_draws, site=None):
+    """k_learn_pick restated, all in integers: draw d takes argmin_i mix64(keys[i] ^ salt_d), the lower slot winning equal values;
+    salt_d from RL_SITE_LEARN (site: another Philox site -- RL_SITE_LEARN_PRIO for the prioritised draw with no weight anywhere)."""
+    from reinlife_amd import _lib
+    keys = np.asarray(keys, np.uint64)
+    salts = _salts(seed, brain, calls, _lib.SITE_LEARN if site is None else site, n_draws)
+    return np.array([int(np.argmin(_mix64(keys ^ s))) for s in salts], np.int64)   # (argmin: the first of equal values)
+
+
+def host_draw64(keys, weight32, seed, brain, calls, n_draws):
+    """host_draw's integer part with t = -log(U) / weight in float64, from the float32 weights the device itself made (learner.weight
+    read back), so that powf's rounding stays out of the comparison -> (the winner of every draw by (t, v, slot), the relative gap
+    (t_second - t_first) / t_first of every draw: +inf where no second row has a weight)."""
+    from reinlife_amd import _lib
+    keys, w = np.asarray(keys, np.uint64), np.asarray(weight32).astype(np.float64)
+    slot = np.arange(len(keys))
+    rows, gaps = np.zeros(n_draws, np.int64), np.zeros(n_draws)
+    for d, s in enumerate(_salts(seed, brain, calls, _lib.SITE_LEARN_PRIO, n_draws)):
+        v = _mix64(keys ^ s)
+        u = ((v >> np.uint64(41)).astype(np.float64) + 0.5) / 8388608.0
+        t = np.full(len(keys), np.inf)
+        t[w > 0] = -np.log(u[w > 0]) / w[w > 0]
+        order = np.lexsort((slot, v, t))
+        rows[d] = order[0]
+        first, second = t[order[0]], (t[order[1]] if len(keys) > 1 else np.inf)
+        gaps[d] = (second - first) / first if np.isfinite(second) else np.inf
+    return rows, gaps
+
+
+def edge_priorities(n, seed=5):
+    """The priorities of the row-for-row draw tests: random^3 * 4 (weights over several orders of magnitude), every 7th row 0 -- no
+    zeros on a ring of at most three rows."""
+    pri = (np.random.RandomState(seed).random_sample(n) ** 3 * 4).astype(np.float32)
+    if n > 3:
+        pri[::7] = 0.0
+    return pri
