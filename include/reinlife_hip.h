@@ -16,6 +16,7 @@
  *   rl_render          Visualize.render()'s drawing of one frame, for any set of worlds     Helpers/render.py:51-239
  *   rl_learn           DQNAgent.train(): the size gate, 5 minibatch updates (smooth-L1, Adam) and the target copy
  *                      Models/DQN.py:80-83, 142-153 (sampling: :99-113, with replacement here)
+ *   rl_learn_ppo       PPO.learn(): k_epoch full-batch Adam steps on a rollout of at most 32 rows (rl_learn_rollout draws it)
  *   rl_learn_dueling   D3QNAgent.train(): one minibatch update of the dueling network (MSE, Adam), batch up to 64
  *                      Models/D3QN.py:97-116, 148-165 (schedule and target copy of :118-126: the caller's)
  *
@@ -65,7 +66,7 @@ enum { RL_DQN = 0, RL_D3QN = 1, RL_PERD3QN = 2, RL_PPO = 3, RL_PERDQN = 4 };
 /* Philox draw sites */
 enum { RL_SITE_FOOD = 1, RL_SITE_REPRO = 2, RL_SITE_BIRTH = 3, RL_SITE_PRODUCE = 4, RL_SITE_ACT = 5,
        RL_SITE_RESET_AGENT = 6, RL_SITE_RESET_FOOD = 7, RL_SITE_RESET_POISON = 8, RL_SITE_RESET_SUPER = 9, RL_SITE_LEARN = 10,
-       RL_SITE_LEARN_PRIO = 11 };
+       RL_SITE_LEARN_PRIO = 11, RL_SITE_LEARN_ROLLOUT = 12 };
 
 /* keyword arguments of Environment(...) that matter on the path (environment.py:74-89) */
 typedef struct {
@@ -177,7 +178,7 @@ int rl_bind_state(rl_world* h, const rl_state* device_ptrs);
  *   3  a world's agent list outgrew slot_cap                                 detail: slots
  *   4  a taped produce_choice outside [0, RL_N_BEST)                         detail: value
  *   5  rl_render: a world id outside [0, n_worlds) ([1] = the id)            detail: frame index
- *   6  rl_learn: a minibatch slot outside [0, ring size) ([1] = brain index) detail: step, value */
+ *   6  rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo: a minibatch slot outside [0, ring size) ([1] = brain index) detail: step, value */
 int rl_bind_error_flag(rl_world* h, int32_t* device_flag);
 
 /* tuning aid: device int64[32] receiving shader-clock stamps at the phase boundaries of world `world` (NULL = off) */
@@ -445,6 +446,58 @@ int rl_learn_prioritized_supported(int kind);
  * rl_learn, rl_learn_draw, rl_learn_dueling and the two older *_supported answers are unchanged by it. */
 int rl_learn_prioritized(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners, int n_steps,
                          const int32_t* slots, void* stream);
+
+/* ---- on-policy learning (PPO) ------------------------------------------------------------------------------------ */
+#define RL_PPO_ROLLOUT_MAX 32
+/* What a learning PPO brain needs beside its rl_learner and its rl_replay ring (which must carry `prob`): the hyperparameters of
+ * Models/PPO.py:42-43 and the bookkeeping of the on-policy window, as caller-owned device buffers. */
+typedef struct {
+    float lmbda, eps_clip;      /* 0.95, 0.1 (PPO.py:42) */
+    int32_t k_epoch;            /* Adam steps per rollout, 1..8 (PPO.py:43: 3) */
+    unsigned long long* seen;   /* [1] initialise to 0: ring.count as of the last rl_learn_rollout */
+    unsigned long long* fresh;  /* [1] written by rl_learn_rollout: the rows of its window; rl_learn_ppo: may be NULL (always train) */
+    unsigned long long* keys;   /* [capacity] scratch of rl_learn_rollout: content keys as rl_learn_draw makes them */
+} rl_ppo;
+/* 1 for the brain kinds rl_learn_ppo trains (RL_PPO), 0 for the others */
+int rl_learn_ppo_supported(int kind);
+/* PPO.learn() (Models/PPO.py:136-162) for n_learners brains in ONE stream-ordered launch, one workgroup per brain: n_steps rollouts per
+ * brain, one after the other, each the reference's learn() on the rows slots[i][s][0 .. batch) IN THAT ORDER (the GAE's order).
+ * rl_learner is reused: kind = RL_PPO; params, adam_m, adam_v, state, packed; lr, gamma, beta1, beta2, eps; batch = the rows of a
+ * rollout, in [1, RL_PPO_ROLLOUT_MAX]; target, min_size and sync_target are ignored (target may be NULL).
+ *   network     fc1 153->256, fc2 256->256, fc_pi 256->8, fc_v 256->1, ReLU after fc1 and fc2: 107,529 parameters, state-dict order
+ *   a rollout   k_epoch full-batch Adam steps, each from the current parameters: reward / 100 (in double, rounded to float, PPO.py:73);
+ *               td = r + gamma v(s') (1 - done); delta = td - v(s); adv_t = gamma lmbda adv_(t+1) + delta_t backwards over the rows with
+ *               no reset at done, in float32 ((float)(gamma * lmbda), one multiply, one add, no fma: what numpy 2 makes of PPO.py:144-150;
+ *               numpy 1 would make it double); ratio = exp(log pi(s)[a] - log prob_a); surr1 = ratio adv, surr2 = clamp(ratio, 1 - eps_clip,
+ *               1 + eps_clip) adv; loss = mean(-min(surr1, surr2)) + smooth_l1(v(s), td) (beta 1).  Nothing flows through v(s') or the
+ *               advantage.  At the kinks the gradient is torch's: min gives the smaller side all of it and each side half at a tie,
+ *               clamp passes it on [1 - eps_clip, 1 + eps_clip], bounds included.  Adam exactly as rl_learn_dueling makes it (double
+ *               update, bias corrections in double from state[0], lr / betas / eps -- and here gamma, lmbda, eps_clip -- re-read as decimals).
+ *   rows        slots: device int32 [n_learners][n_steps][batch]; NULL is refused (RL_E_INVALID): rl_learn_rollout draws them.  All are
+ *               range-checked against [0, min(count, capacity)) before the first row is fetched: a bad one sets error-flag code 6 and
+ *               that brain leaves with NONE of its buffers written (the others train).
+ *   fresh       ppos[i].fresh given and *fresh == 0: no update and no slot check (`if self.data()`, PPO.py:76); only state[1] moves.
+ *   afterwards  state[0] += k_epoch per rollout trained; state[1] += 1; `packed` is rewritten from the final params, bit for bit what
+ *               rl_policy_pack_weights(RL_PPO, ...) makes.  loss [n_steps][k_epoch] and grad [n_steps * k_epoch][n_params] are written when given.
+ * Validation: kind must be RL_PPO (anything else: RL_E_UNSUPPORTED naming the kind); batch in [1,32]; k_epoch in [1,8]; at most
+ * RL_MAX_CAPTURE_BRAINS learners; the ring must carry `prob`.  Deterministic like rl_learn_dueling: plain f32 FMA, every sum by one thread in
+ * a fixed order, no float atomics.  rl_learn, rl_learn_dueling, rl_learn_prioritized and their *_supported answers are unchanged by it. */
+int rl_learn_ppo(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_ppo* ppos, int n_learners, int n_steps,
+                 const int32_t* slots, void* stream);
+/* The on-policy counterpart of rl_learn_draw: the `slots` of an rl_learn_ppo call, drawn from the rows appended since the last call --
+ * PPO trains on rows its current weights made -- and, like rl_learn_draw, without depending on the slots the rows sit in.
+ *   window   slots [*seen, *count) mod capacity, or the whole ring once count - seen >= capacity
+ *   draws    each of the n_steps * batch draws d takes the window row whose content key (rl_learn_draw's, unchanged), mixed with words
+ *            0-1 of rl_philox(seed, 0, i, (uint32)state[1], RL_SITE_LEARN_ROLLOUT, d), is smallest: uniform over the fresh rows, WITH
+ *            replacement, the same rows whatever slots they sit in.  An empty window draws slot 0.
+ *   writes   keys of the window's rows, slots (the learners' [n_steps][batch] tables laid end to end), *fresh = the rows of the window,
+ *            then *seen = *count.
+ * Two launches, no allocation.  kind must be RL_PPO; rings need state / state_prime / action / reward / done / age / count; seen, fresh
+ * and keys of every rl_ppo must be set; batch in [1,32].  Deviations from the reference: a rollout is `batch` independent draws, so the
+ * GAE's neighbours are unrelated rows (in the reference: unrelated agents of one tick); all but n_steps * batch of the fresh rows go
+ * unused; a launch that appends more than a ring holds keeps rows by append order. */
+int rl_learn_rollout(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_ppo* ppos, int n_learners, int n_steps,
+                     int32_t* slots, void* stream);
 
 /* ---- frames ---------------------------------------------------------------------------------------------------- */
 /* What the painter of Helpers/render.py:51-239 draws, as integers: pixels per cell, the body square (offset, side, border width), the

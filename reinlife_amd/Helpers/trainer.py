@@ -19,7 +19,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
             print_results=True, max_agents=100, render=False, static_families=True, training=True, save=True,
             limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None, seed=0, rng=None, per_agent_api=False,
             fused=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
-            learn_steps=5, learn_kinds=None, learn_prioritized=None):
+            learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1):
     """Extra keyword-only arguments: n_worlds / device / seed / rng / synthetic_agents / refill_below (Environment); per_agent_api=True makes the reference's literal
     per-agent get_action / learn calls; fused (default: True for rng="philox" without per_agent_api) runs the loop through
     Environment.run -- whole chunks of ticks per launch, ending where the Tracker closes an interval -- instead of three launches
@@ -65,7 +65,17 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     brain trains once per `learn_every` episodes, so ALL rows appended between two calls get the maximum as of the earlier call (the
     reference's per-agent train() calls change it in between); draws are by content key.  The run-to-run caveat is sharper here: a ring
     holds only 10,000 rows and a chunk of 256 worlds appends far more than that, so which rows survive depends on append order --
-    a second identical call repeats bit for bit only while no chunk appends more than the ring holds."""
+    a second identical call repeats bit for bit only while no chunk appends more than the ring holds.
+    learn_rollout (default None: every run is what it was; True needs learn="device" and at least one Models.PPO, ValueError otherwise,
+    before a device is touched; it needs no learn_kinds; a PPO's train_freq sets the default `learn_every` only where PPO brains are
+    the only learners): every PPO brain trains through rl_learn_ppo.  The rings then also record the acting probability of every row
+    (PPO.py:73).  After every episode that is a multiple of `learn_every`, behind the DQN, D3QN and PERD3QN calls (which stay bit for
+    bit what they are without the keyword), one on-policy draw (rl_learn_rollout, two launches) names `rollout_steps` (default 1)
+    rollouts of 32 rows among the rows appended since the last call, and ONE rl_learn_ppo makes PPO.learn() (PPO.py:136-162) on each:
+    k_epoch (3) full-batch Adam steps on the clipped surrogate plus the smooth-L1 value loss, GAE backwards over the rollout's rows.
+    DEVIATIONS: the schedule (once per `learn_every` episodes, not per agent); a rollout is 32 independent draws with replacement, so
+    the GAE's neighbours are unrelated rows -- in the reference they are unrelated agents of one tick; all but rollout_steps * 32 of the
+    fresh rows go unused; a chunk that appends more than a ring holds keeps rows by append order."""
     if learn == "device" and (per_agent_api or fused is False):
         raise ValueError("trainer(learn='device') needs the fused path (fused=True, per_agent_api=False): the replay rings are filled "
                          "inside the multi-tick launches")
@@ -75,7 +85,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
                       limit_reproduction=limit_reproduction, incentivize_killing=incentivize_killing, n_worlds=n_worlds,
                       device=device, seed=seed, rng=rng, synthetic_agents=synthetic_agents, refill_below=refill_below, dist=dist,
                       world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps, learn_kinds=learn_kinds,
-                      learn_prioritized=learn_prioritized)
+                      learn_prioritized=learn_prioritized, learn_rollout=learn_rollout, rollout_steps=rollout_steps)
     env.reset()
     if fused is None:
         fused = env.rng == "philox" and not per_agent_api

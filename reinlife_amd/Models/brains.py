@@ -235,6 +235,8 @@ class PPOAgent(_HipBrain):
                  train_freq=20, load_model=False):
         super().__init__(input_dim, output_dim, "PPO")
         self.model = _PPONet(input_dim, output_dim)
+        # (read by learn.DeviceLearner(..., rollout=True); the reference hands them to its PPO module, PPO.py:46)
+        self.learning_rate, self.gamma, self.lmbda, self.eps_clip, self.k_epoch = learning_rate, gamma, lmbda, eps_clip, k_epoch
         self.load_model = load_model
         self.train_freq = train_freq
         self.epsilon = 0.0

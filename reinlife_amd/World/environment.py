@@ -158,7 +158,7 @@ class Environment:
                  static_families=True, interactive_results=False, google_colab=False, training=True, save=False,
                  pastel_colors=False, limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None,
                  seed=0, rng=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
-                 learn_steps=5, learn_kinds=None, learn_prioritized=None):
+                 learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1):
         if not brains:
             raise ValueError("Environment needs a non-empty list of brains")
         if learn not in (None, "device"):
@@ -182,6 +182,19 @@ class Environment:
         if learn_prioritized and not any(getattr(b, "method", None) == "PERD3QN" for b in brains):
             raise ValueError("learn_prioritized=True needs at least one Models.PERD3QN brain (got %s)" % ", ".join(str(getattr(b, "method", b)) for b in brains))
         self.learn_prioritized = bool(learn_prioritized)
+        # learn_rollout=True: every PPO brain trains through rl_learn_ppo on rollouts drawn from the rows its current weights made
+        # (PPO.py:71-77, 136-162).  A keyword of its own, like learn_prioritized.  Checked before a device is touched.
+        if learn_rollout not in (None, True):
+            raise ValueError("learn_rollout must be None or True, got %r" % (learn_rollout,))
+        if learn_rollout and learn != "device":
+            raise ValueError("learn_rollout=True needs learn='device' (got learn=%r)" % (learn,))
+        if learn_rollout and not any(getattr(b, "method", None) == "PPO" for b in brains):
+            raise ValueError("learn_rollout=True needs at least one Models.PPO brain (got %s)" % ", ".join(str(getattr(b, "method", b)) for b in brains))
+        if rollout_steps != 1 and not learn_rollout:
+            raise ValueError("rollout_steps needs learn_rollout=True")
+        if int(rollout_steps) < 1:
+            raise ValueError("rollout_steps must be >= 1 (got %r)" % (rollout_steps,))
+        self.learn_rollout, self.rollout_steps = bool(learn_rollout), int(rollout_steps)
         # learn_steps: minibatch updates per call -- an int is the DQN learners' (as always), a dict by method name sets it per kind;
         # D3QN defaults to 1 (D3QNAgent.train() makes one update)
         self.learn_steps_of = {"DQN": 5, "D3QN": 1}
@@ -281,26 +294,33 @@ class Environment:
             entries = {k: entry_of(b.kind) for k, b in enumerate(brains) if b.method in self.learn_kinds}
             entries = {k: e for k, e in entries.items() if e is not None}
             prio = [k for k, b in enumerate(brains) if self.learn_prioritized and b.method == "PERD3QN"]
+            ppo = [k for k, b in enumerate(brains) if self.learn_rollout and b.method == "PPO"]
+            prob = {"with_prob": True} if ppo else {}   # the acting probability of every row (PPO.py:73): only where a PPO brain learns
             if prio or any(e == "rl_learn_dueling" for e in entries.values()):
                 # a D3QN or prioritised PERD3QN learner's ring holds its brain's `capacity` rows (D3QN.py:62, PERD3QN.py:49, 55: 10,000);
                 # every other ring stays DQN.py:15's
-                self.worlds.enable_capture([int(b.capacity) if (entries.get(k) == "rl_learn_dueling" or k in prio) else BUFFER_LIMIT for k, b in enumerate(brains)])
+                self.worlds.enable_capture([int(b.capacity) if (entries.get(k) == "rl_learn_dueling" or k in prio) else BUFFER_LIMIT for k, b in enumerate(brains)], **prob)
             else:
-                self.worlds.enable_capture(BUFFER_LIMIT)
+                self.worlds.enable_capture(BUFFER_LIMIT, **prob)
             for k in entries:
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k])
             for k in prio:
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], prioritized=True)
+            for k in ppo:
+                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], rollout=True)
             if not self.learners:
                 raise ValueError("learn='device': none of the brains is of a kind rl_learn trains (DQN)" if self.learn_kinds == ("DQN",) else
                                  "learn='device': none of the brains is of a kind in learn_kinds %r" % (self.learn_kinds,))
             # the default period is the smallest train_freq of the learners a run has WITHOUT learn_prioritized, so that the keyword does
-            # not move their schedule; the prioritised learners' own train_freq counts only where they are the only learners
-            timed = [l for l in self.learners.values() if l.entry != "rl_learn_prioritized"] or list(self.learners.values())
+            # not move their schedule; the prioritised learners' own train_freq counts only where they are the only learners -- and
+            # likewise learn_rollout and the PPO learners'
+            timed = ([l for l in self.learners.values() if l.entry not in ("rl_learn_prioritized", "rl_learn_ppo")]
+                     or [l for l in self.learners.values() if l.entry != "rl_learn_ppo"] or list(self.learners.values()))
             self.learn_every = int(learn_every) if learn_every is not None else min(l.train_freq for l in timed)
             frozen = ["%d (%s)" % (k, b.method) for k, b in enumerate(brains) if k not in self.learners]
             if frozen:
-                warn_inference_only(frozen, self.learn_kinds + (("PERD3QN (prioritised)",) if self.learn_prioritized else ()))
+                warn_inference_only(frozen, self.learn_kinds + (("PERD3QN (prioritised)",) if self.learn_prioritized else ())
+                                    + (("PPO (rollouts)",) if self.learn_rollout else ()))
         elif training:
             warn_inference_only()
 
@@ -600,8 +620,14 @@ class Environment:
                         "exploration, target synced every soft_update_freq episodes, rows drawn with probability priority^0.6 / sum by content key "
                         "with replacement; rows appended between two calls get the priority maximum as of the earlier call)"
                         % (prio, sorted({self.learners[k].batch for k in prio}), self.learn_every))
+        ppo = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_ppo")
+        if ppo:
+            note.append("brains %s trained on the device (rl_learn_ppo: %d rollout(s) of %s rows, %s Adam steps each, every %d episodes; the rows are "
+                        "drawn by content key with replacement from those appended since the last call, so the GAE's neighbours are unrelated rows "
+                        "and the other fresh rows go unused)"
+                        % (ppo, self.rollout_steps, sorted({self.learners[k].batch for k in ppo}), sorted({self.learners[k].k_epoch for k in ppo}), self.learn_every))
         if frozen:
-            note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if (duel or prio) else
+            note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if (duel or prio or ppo) else
                         "brains %s as loaded / initialised (their kinds do not learn in this build)" % frozen)
         return "; ".join(note)
 
@@ -614,7 +640,10 @@ class Environment:
         in (last - learn_every, last].  last=None: every D3QN learner trains, sync_target as the learner holds it.
         Prioritised PERD3QN learners (learn_prioritized=True) follow on the same schedule (PERD3QN.py:117-125 is D3QN.py:118-126), behind
         the DQN and D3QN calls, which stay what they are without them: one prioritised draw (DeviceWorlds.draw_prioritized, two launches)
-        and one rl_learn_prioritized, ONE update per call as PERD3QNAgent.train() makes."""
+        and one rl_learn_prioritized, ONE update per call as PERD3QNAgent.train() makes.
+        PPO learners (learn_rollout=True) come last, behind those calls, which again stay what they are without them: one on-policy draw
+        (DeviceWorlds.draw_rollout, two launches) and one rl_learn_ppo of `rollout_steps` rollouts (PPO.learn(), PPO.py:136-162), on
+        every call -- PPO has no exploration gate; a window without fresh rows makes no update."""
         dqn = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn"]
         if dqn:
             self.worlds.learn(dqn, self.learn_steps, slots=self.worlds.draw_slots(dqn, self.learn_steps))
@@ -635,6 +664,9 @@ class Environment:
                 for l in ls:
                     l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
             self.worlds.learn(ls, 1, slots=self.worlds.draw_prioritized(ls, 1))
+        ppo = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_ppo"]
+        if ppo:
+            self.worlds.learn(ppo, self.rollout_steps, slots=self.worlds.draw_rollout(ppo, self.rollout_steps))
 
     def sync_learners(self):
         """The trained parameters into the brains' modules (DeviceLearner.sync_to_module): what Saver and state_dict() read."""
@@ -784,7 +816,8 @@ def warn_inference_only(frozen=None, kinds=("DQN",)):
         if tuple(kinds) == ("DQN",):
             warnings.warn("learn='device' trains the DQN brains of this run; brains %s are of kinds rl_learn does not train yet: they stay "
                           "inference only -- brain.learn() is a no-op for them and their weights are NOT updated (D3QN brains learn with "
-                          "learn_kinds=('DQN', 'D3QN'), PERD3QN brains with learn_prioritized=True)." % ", ".join(frozen), stacklevel=3)
+                          "learn_kinds=('DQN', 'D3QN'), PERD3QN brains with learn_prioritized=True, PPO brains with learn_rollout=True; PERDQN brains do "
+                          "not learn yet)." % ", ".join(frozen), stacklevel=3)
         else:
             warnings.warn("learn='device' trains the %s brains of this run; brains %s are of other kinds (or of kinds no entry point trains): they stay "
                           "inference only -- brain.learn() is a no-op for them and their weights are NOT updated." % (" and ".join(kinds), ", ".join(frozen)), stacklevel=3)

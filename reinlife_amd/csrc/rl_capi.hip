@@ -35,6 +35,9 @@ int rl_learn_dueling_launch(rl_world*, const rl_learner*, const rl_replay*, int,
 int rl_learn_prioritized_supported_impl(int);
 int rl_learn_prioritized_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_prio*, int, int, const int32_t*, hipStream_t);
 int rl_learn_prioritized_draw_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_prio*, int, int, int32_t*, hipStream_t);
+int rl_learn_ppo_supported_impl(int);
+int rl_learn_ppo_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, const int32_t*, hipStream_t);
+int rl_learn_rollout_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, int32_t*, hipStream_t);
 
 static thread_local char g_err[512] = "";
 
@@ -504,6 +507,62 @@ int rl_learn_prioritized(rl_world* h, const rl_learner* learners, const rl_repla
     if (int rc = check_prioritized("rl_learn_prioritized", false, h, learners, rings, prios, n_learners, n_steps, slots)) return rc;
     DeviceGuard guard(device_of_pointer(learners[0].params));
     return rl_learn_prioritized_launch(h, learners, rings, prios, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+int rl_learn_ppo_supported(int kind) { return rl_learn_ppo_supported_impl(kind); }
+
+// what rl_learn_ppo and rl_learn_rollout ask of their common arguments (`draw`: the rollout draw needs the rings' age column and
+// seen / fresh / keys of rl_ppo; the update needs the learner's buffers and the rings' prob column)
+static int check_ppo(const char* who, bool draw, rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_ppo* ppos,
+                     int n_learners, int n_steps, const void* slots)
+{
+    if (!h) { rl_set_error("%s: null handle", who); return RL_E_INVALID; }
+    if (!learners || !rings || !ppos) { rl_set_error("%s: null learners / rings / ppos", who); return RL_E_INVALID; }
+    if (n_learners < 1 || n_learners > RL_MAX_CAPTURE_BRAINS) { rl_set_error("%s: n_learners must be in [1,%d] (got %d)", who, RL_MAX_CAPTURE_BRAINS, n_learners); return RL_E_INVALID; }
+    if (n_steps < 1 || n_steps > 65536) { rl_set_error("%s: n_steps must be in [1,65536] (got %d)", who, n_steps); return RL_E_INVALID; }
+    if (!slots) {
+        rl_set_error(draw ? "%s: slots must not be null" : "%s: slots must not be null -- the rows of a rollout are drawn by rl_learn_rollout (or named by the caller)", who);
+        return RL_E_INVALID;
+    }
+    for (int i = 0; i < n_learners; ++i) {
+        const rl_learner& l = learners[i];
+        const rl_replay& r = rings[i];
+        const rl_ppo& p = ppos[i];
+        if (!rl_learn_ppo_supported_impl(l.kind)) { rl_set_error("%s: learner %d has brain kind %d; this entry point trains RL_PPO (3) only (rl_learn_ppo_supported)", who, i, l.kind); return RL_E_UNSUPPORTED; }
+        if (draw) {
+            if (!l.state) { rl_set_error("%s: learner %d: state must not be null", who, i); return RL_E_INVALID; }
+        } else if (!l.params || !l.adam_m || !l.adam_v || !l.state || !l.packed) {
+            rl_set_error("%s: learner %d: params / adam_m / adam_v / state / packed must not be null", who, i); return RL_E_INVALID;
+        }
+        if (l.batch < 1 || l.batch > RL_PPO_ROLLOUT_MAX) { rl_set_error("%s: learner %d: batch (the rows of a rollout) must be in [1,%d] (got %d)", who, i, RL_PPO_ROLLOUT_MAX, l.batch); return RL_E_INVALID; }
+        if (!r.state || !r.state_prime || !r.action || !r.reward || !r.done || !r.count || (draw && !r.age) || r.capacity < 1 || r.capacity > 0x7fffffff) {
+            rl_set_error("%s: replay %d incomplete (state / state_prime / action / reward / done / %scount, capacity in [1, 2^31))", who, i, draw ? "age / " : ""); return RL_E_INVALID;
+        }
+        if (draw) {
+            if (!p.seen || !p.fresh || !p.keys) { rl_set_error("%s: ppo %d: seen / fresh / keys must not be null", who, i); return RL_E_INVALID; }
+        } else {
+            if (!r.prob) { rl_set_error("%s: replay %d has no prob column: a PPO brain's ring records the acting probability (rl_run_opts.policy_out)", who, i); return RL_E_INVALID; }
+            if (p.k_epoch < 1 || p.k_epoch > 8) { rl_set_error("%s: ppo %d: k_epoch must be in [1,8] (got %d)", who, i, p.k_epoch); return RL_E_INVALID; }
+            if (!(p.eps_clip >= 0.0f) || !(p.lmbda >= 0.0f)) { rl_set_error("%s: ppo %d: lmbda and eps_clip must be >= 0 (got %g, %g)", who, i, (double)p.lmbda, (double)p.eps_clip); return RL_E_INVALID; }
+        }
+    }
+    return RL_OK;
+}
+
+int rl_learn_ppo(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_ppo* ppos, int n_learners, int n_steps,
+                 const int32_t* slots, void* stream)
+{
+    if (int rc = check_ppo("rl_learn_ppo", false, h, learners, rings, ppos, n_learners, n_steps, slots)) return rc;
+    DeviceGuard guard(device_of_pointer(learners[0].params));
+    return rl_learn_ppo_launch(h, learners, rings, ppos, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+int rl_learn_rollout(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_ppo* ppos, int n_learners, int n_steps,
+                     int32_t* slots, void* stream)
+{
+    if (int rc = check_ppo("rl_learn_rollout", true, h, learners, rings, ppos, n_learners, n_steps, slots)) return rc;
+    DeviceGuard guard(device_of_pointer(slots));
+    return rl_learn_rollout_launch(h, learners, rings, ppos, n_learners, n_steps, slots, (hipStream_t)stream);
 }
 
 int rl_render(rl_world* h, const rl_render_style* style, const int32_t* worlds, int n_frames, uint8_t* frames, void* stream)

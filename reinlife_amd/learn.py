@@ -20,7 +20,17 @@ agent's learner (rl_learn_prioritized): besides the D3QN learner's tensors it ow
 maximum, the ring count as of the last draw, and two scratch columns of the draw (DeviceWorlds.draw_prioritized: probability
 priority^0.6 / sum, with replacement, by content key).  Its only size gate is np.random.choice's need of one row (min_size = 0).  The
 same two deviations apply, and one more follows from the first: every row appended between two learning calls gets the priority
-maximum as of the earlier call."""
+maximum as of the earlier call.
+
+PPOAgent (ReinLife/Models/PPO.py:10-77) owns one module, `model`, with its own Adam (PPO.py:99) and the list of transitions gathered since
+the last learn() (PPO.py:88, 114-115); learn() (PPO.py:136-162) makes k_epoch full-batch Adam steps on that list and empties it.
+DeviceLearner(brain, device, ring, rollout=True) is that agent's learner (rl_learn_ppo): the parameters, Adam's moments, the counters and
+the packed weights as above (no target network), lr / gamma / lmbda / eps_clip / k_epoch from the brain, and beside the ring -- which must
+carry the acting probability (enable_capture(..., with_prob=True)) -- the bookkeeping of the on-policy window: the ring count as of the last
+rollout, the rows the last window held, and the draw's scratch keys (DeviceWorlds.draw_rollout: `batch` = 32 rows per rollout, drawn
+uniformly with replacement by content key from the rows appended since the last call).  Deviations: the schedule is the caller's; a rollout
+is 32 independent draws, so the GAE recursion's neighbours are unrelated rows (in the reference: unrelated agents of one tick); the fresh
+rows not drawn go unused."""
 import copy
 import ctypes as C
 
@@ -40,9 +50,14 @@ def entry_of(kind):
 
 
 class DeviceLearner:
-    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False):
+    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False):
         lib = _lib.lib()
-        if prioritized:   # an explicit opt-in: entry_of() and ENTRY_BY_METHOD keep answering what they answered
+        if rollout:   # an explicit opt-in, like prioritized: entry_of() and ENTRY_BY_METHOD keep answering what they answered
+            if prioritized or not lib.rl_learn_ppo_supported(brain.kind):
+                raise ValueError("rollout=True is for PPO brains (rl_learn_ppo); got a %s brain (kind %d)%s"
+                                 % (brain.method, brain.kind, " with prioritized=True" if prioritized else ""))
+            self.entry = "rl_learn_ppo"
+        elif prioritized:   # an explicit opt-in: entry_of() and ENTRY_BY_METHOD keep answering what they answered
             if not lib.rl_learn_prioritized_supported(brain.kind):
                 raise ValueError("prioritized=True is for PERD3QN brains (rl_learn_prioritized); got a %s brain (kind %d)" % (brain.method, brain.kind))
             self.entry = "rl_learn_prioritized"
@@ -56,13 +71,19 @@ class DeviceLearner:
         flat = brain.state_dict_flat()
         self.n_params = int(lib.rl_policy_n_params(self.kind))
         self.params = torch.as_tensor(flat, device=self.device)
-        self.target = self.params.clone()                       # DQN.py:50 / D3QN.py:60
+        self.target = None if rollout else self.params.clone()  # DQN.py:50 / D3QN.py:60 (PPO has no target network)
         self.adam_m = torch.zeros_like(self.params)
         self.adam_v = torch.zeros_like(self.params)
         self.state = torch.zeros(2, dtype=torch.int64, device=self.device)   # [Adam steps taken, rl_learn calls made]
         self.packed = pack_brain_weights(self.kind, flat, self.device)
         self.train_freq = int(getattr(brain, "train_freq", 20))
-        if self.entry == "rl_learn":
+        if self.entry == "rl_learn_ppo":   # PPO.py:42-43: the brain's own hyperparameters
+            self.lr, self.gamma = float(getattr(brain, "learning_rate", 0.0005)), float(getattr(brain, "gamma", 0.98))
+            self.lmbda, self.eps_clip, self.k_epoch = float(getattr(brain, "lmbda", 0.95)), float(getattr(brain, "eps_clip", 0.1)), int(getattr(brain, "k_epoch", 3))
+            self.batch, self.min_size = _lib.PPO_ROLLOUT_MAX, 0  # the rows of a rollout; no size gate (an empty window makes no update)
+            self.n_steps_default = 1                             # one PPO.learn() per call
+            self.sync_target = False
+        elif self.entry == "rl_learn":
             self.lr = float(getattr(brain, "learning_rate", 0.0005))
             self.gamma, self.batch, self.min_size = GAMMA, BATCH, MIN_SIZE
             self.n_steps_default = 5                             # DQN.py:143
@@ -81,6 +102,9 @@ class DeviceLearner:
         self.priority = self.weight = self.keys = self.prio_max = self.seen = None
         if prioritized and ring is not None:
             self._make_prio()
+        self.fresh = None         # rollout=True: the window's bookkeeping (seen and keys above, fresh here)
+        if rollout and ring is not None:
+            self._make_ppo()
         self.loss = None          # optional device float32 [n_steps]
         self.grad = None          # optional device float32 [n_steps, n_params] (tests, diagnostics)
 
@@ -117,6 +141,24 @@ class DeviceLearner:
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         return _lib.Prio(p(self.priority), p(self.weight), p(self.keys), p(self.prio_max), p(self.seen), self.alpha)
 
+    def _make_ppo(self):
+        """The on-policy window's bookkeeping beside the ring (rl_ppo), sized to it: nothing seen, no fresh rows."""
+        capacity = int(self.ring["state"].shape[0])
+        self.keys = torch.zeros(capacity, dtype=torch.int64, device=self.device)
+        self.seen = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.fresh = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def ppo_struct(self, gate=True):
+        """rl_ppo.  gate=False leaves `fresh` out: rl_learn_ppo then trains on the slots it is given whatever the last rollout's window held."""
+        if self.entry != "rl_learn_ppo":
+            raise _lib.ReinLifeHipError("this DeviceLearner is no PPO learner (DeviceLearner(..., rollout=True))")
+        if self.ring is None:
+            raise _lib.ReinLifeHipError("this DeviceLearner has no replay ring (DeviceLearner.ring)")
+        if self.fresh is None or self.keys.numel() != self.ring["state"].shape[0]:
+            self._make_ppo()
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        return _lib.Ppo(self.lmbda, self.eps_clip, self.k_epoch, p(self.seen), p(self.fresh) if gate else None, p(self.keys))
+
     @property
     def steps(self):
         """Adam steps taken so far (reads the device counter: synchronises)."""
@@ -134,6 +176,9 @@ class DeviceLearner:
     def sync_to_module(self):
         """The trained parameters into brain.agent and the target network's into brain.target (made on first use: a copy, no
         generator draw), so that Saver and state_dict() see them.  D3QN and PERD3QN: into brain.eval_net and brain.target_net."""
+        if self.entry == "rl_learn_ppo":   # PPO.py:46: one module, no target
+            self._load(self.brain.model, self.params.cpu().numpy())
+            return
         if self.entry in ("rl_learn_dueling", "rl_learn_prioritized"):
             self._load(self.brain.eval_net, self.params.cpu().numpy())
             self._load(self.brain.target_net, self.target.cpu().numpy())

@@ -466,7 +466,28 @@ class DeviceWorlds:
         self.launches += 2
         return slots
 
-    def learn(self, learners, n_steps, slots=None):
+    def draw_rollout(self, learners, n_steps):
+        """The rollouts of PPO learners (DeviceLearner(..., rollout=True)) for learn(learners, n_steps, slots=...): the on-policy draw
+        (rl_learn_rollout) -- the window is the rows appended to a ring since the last call (the whole ring once that is more than it
+        holds); each of the n_steps * batch draws takes a window row uniformly, with replacement, by a key of the rows' content: the same
+        rows whatever slots they sit in.  Leaves the number of rows of the window in learner.fresh (an empty one: the following learn()
+        makes no update) and moves learner.seen up.  Device int32 [len(learners), n_steps, batch], queued on the current stream."""
+        n = len(learners)
+        if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
+            raise ValueError("draw_rollout(): 1 to %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
+        if len({l.batch for l in learners}) != 1:
+            raise ValueError("draw_rollout(): the learners of a call must share one batch size")
+        if any(l.entry != "rl_learn_ppo" for l in learners):
+            raise ValueError("draw_rollout(): every learner must be a PPO one (DeviceLearner(..., rollout=True))")
+        arr = (_lib.Learner * n)(*[l.struct() for l in learners])
+        rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
+        ppos = (_lib.Ppo * n)(*[l.ppo_struct() for l in learners])
+        slots = torch.zeros((n, int(n_steps), int(learners[0].batch)), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.rl_learn_rollout(self.handle, arr, rings, ppos, n, int(n_steps), _ptr(slots), self._stream()), "rl_learn_rollout")
+        self.launches += 2
+        return slots
+
+    def learn(self, learners, n_steps, slots=None, gate=True):
         """DQNAgent.train() (DQN.py:80-83, 142-153) for every DeviceLearner of `learners` in ONE launch (rl_learn), queued on the current
         stream behind the ticks launched so far: `n_steps` minibatch updates per brain on its replay ring (learner.ring), then the
         target copy, and the learner's packed weights rewritten in place -- brains bound with that tensor act on the new weights
@@ -475,7 +496,9 @@ class DeviceWorlds:
         brain index of the draw is the learner's position in `learners`).
         A list of D3QN learners goes to rl_learn_dueling instead (D3QNAgent.train(), D3QN.py:97-116: batch up to 64, MSE, the target copy
         only when learner.sync_target says so), a list of prioritised PERD3QN learners to rl_learn_prioritized (PERD3QNAgent.train(),
-        PERD3QN.py:94-115: the same update, and the batch rows' priorities rewritten; `slots` must come from draw_prioritized()).  The
+        PERD3QN.py:94-115: the same update, and the batch rows' priorities rewritten; `slots` must come from draw_prioritized()), a list of
+        PPO learners to rl_learn_ppo (PPO.learn(), PPO.py:136-162: n_steps rollouts of `batch` rows, k_epoch Adam steps each; `slots` from
+        draw_rollout(), or the caller's own rows with gate=False, which leaves the empty-window gate out).  The
         learners of one call must all belong to one entry point: ValueError otherwise."""
         if not learners:
             return
@@ -497,6 +520,9 @@ class DeviceWorlds:
         if entry == "rl_learn_prioritized":
             prios = (_lib.Prio * n)(*[l.prio_struct() for l in learners])
             _lib.check(self.lib.rl_learn_prioritized(self.handle, arr, rings, prios, n, int(n_steps), _ptr(slots), self._stream()), entry)
+        elif entry == "rl_learn_ppo":
+            ppos = (_lib.Ppo * n)(*[l.ppo_struct(gate=gate) for l in learners])
+            _lib.check(self.lib.rl_learn_ppo(self.handle, arr, rings, ppos, n, int(n_steps), _ptr(slots), self._stream()), entry)
         else:
             _lib.check(getattr(self.lib, entry)(self.handle, arr, rings, n, int(n_steps), _ptr(slots), self._stream()), entry)
         self._learn_keep = slots   # (the launch reads the table asynchronously)
