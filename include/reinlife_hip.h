@@ -66,7 +66,7 @@ enum { RL_DQN = 0, RL_D3QN = 1, RL_PERD3QN = 2, RL_PPO = 3, RL_PERDQN = 4 };
 /* Philox draw sites */
 enum { RL_SITE_FOOD = 1, RL_SITE_REPRO = 2, RL_SITE_BIRTH = 3, RL_SITE_PRODUCE = 4, RL_SITE_ACT = 5,
        RL_SITE_RESET_AGENT = 6, RL_SITE_RESET_FOOD = 7, RL_SITE_RESET_POISON = 8, RL_SITE_RESET_SUPER = 9, RL_SITE_LEARN = 10,
-       RL_SITE_LEARN_PRIO = 11, RL_SITE_LEARN_ROLLOUT = 12 };
+       RL_SITE_LEARN_PRIO = 11, RL_SITE_LEARN_ROLLOUT = 12, RL_SITE_LEARN_TD = 13 };
 
 /* keyword arguments of Environment(...) that matter on the path (environment.py:74-89) */
 typedef struct {
@@ -178,7 +178,7 @@ int rl_bind_state(rl_world* h, const rl_state* device_ptrs);
  *   3  a world's agent list outgrew slot_cap                                 detail: slots
  *   4  a taped produce_choice outside [0, RL_N_BEST)                         detail: value
  *   5  rl_render: a world id outside [0, n_worlds) ([1] = the id)            detail: frame index
- *   6  rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo: a minibatch slot outside [0, ring size) ([1] = brain index) detail: step, value */
+ *   6  rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo / rl_learn_td: a minibatch slot outside [0, ring size) ([1] = brain index) detail: step, value */
 int rl_bind_error_flag(rl_world* h, int32_t* device_flag);
 
 /* tuning aid: device int64[32] receiving shader-clock stamps at the phase boundaries of world `world` (NULL = off) */
@@ -498,6 +498,66 @@ int rl_learn_ppo(rl_world* h, const rl_learner* learners, const rl_replay* rings
  * unused; a launch that appends more than a ring holds keeps rows by append order. */
 int rl_learn_rollout(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_ppo* ppos, int n_learners, int n_steps,
                      int32_t* slots, void* stream);
+
+/* ---- prioritised replay with importance weights (PERDQN) ---------------------------------------------------------- */
+/* The prioritised memory of one learning PERDQN brain (Memory / SumTree, Models/PERDQN.py) beside its rl_replay ring: caller-owned
+ * device buffers.  Three things the reference does are reproduced as they are (the rule of rl_learn_prioritized):
+ *   1. append_sample's error is |old_val - target[0][action]| with old_val a view of the tensor the line before overwrote: exactly 0.
+ *      EVERY stored row gets (0 + e) ** a as a float32 torch scalar (0.06309573), whatever the row: no forward pass is needed to store
+ *      one, and p_new is that number, made by the caller.
+ *   2. train_model's loss is (FloatTensor(is_weights) * F.mse_loss(pred, target)).mean(), and mse_loss is already the scalar mean:
+ *      loss = mean(is_w) * mean((pred - target)^2).  The importance weights scale the whole batch, not its rows.
+ *   3. Memory.sample's is_weight, (n_entries p_i / total) ** -beta divided by its maximum over the batch, is (p_i / min_j p_j) ** -beta
+ *      over the batch rows: total and n_entries cancel, so the device keeps no sum tree and no total.  beta = min(1, beta + increment),
+ *      in double, at every sample(). */
+typedef struct {
+    float* priority;            /* [capacity] */
+    unsigned long long* keys;   /* [capacity] scratch: content keys as rl_learn_draw makes them */
+    unsigned long long* seen;   /* [1] initialise to 0: ring.count as of the last draw */
+    double* beta;               /* [1] initialise to 0.4 (Memory.beta) */
+    float p_new;                /* priority of a newly stored row: the reference's float32 (0 + e) ** a, made with torch on the host */
+    float prio_e, prio_a;       /* 0.01, 0.6 (Memory.e, Memory.a); prio_a must be > 0 */
+    double beta_increment;      /* 0.001 (Memory.beta_increment_per_sampling) */
+    float* is_weight;           /* [n_steps][batch] or NULL: the importance weights of every step (tests, diagnostics) */
+} rl_tdprio;
+/* 1 for the brain kinds rl_learn_td trains (RL_PERDQN), 0 for the others */
+int rl_learn_td_supported(int kind);
+/* The draw of that memory for n_learners PERDQN brains: rl_learn_prioritized_draw's two launches (no allocation, no host round trip,
+ * independent of the slots the rows sit in) with these differences:
+ *   prepare   the slots in [*seen, *ring.count) mod capacity (all of them when count - seen >= capacity) get priority = p_new, not a
+ *             running maximum; keys[row] as before; there is no weight column
+ *   pick      the race weight is the stored priority itself -- the reference samples in proportion to p, which already carries ** a:
+ *             no powf.  salt_d = words 0-1 of rl_philox(seed, 0, i, (uint32)state[1], RL_SITE_LEARN_TD, d).  t = -logf(U) / priority;
+ *             the smallest (t, v, slot) wins.  A priority of 0 or NaN loses; if every one is zero the draw is rl_learn_draw's uniform
+ *             content-key draw; an empty ring draws slot 0; rows whose t tie are told apart by v.  *seen advances to *ring.count here.
+ * batch in [1,64] directly.  Every learner's kind must be RL_PERDQN (anything else: RL_E_UNSUPPORTED naming the kind); rings need state /
+ * state_prime / action / reward / done / age / count; priority, keys and seen must be set.
+ * Deviation from the reference: Memory.sample is stratified -- one uniform per segment of total / n, found through the sum tree, which
+ * names slots (and the rings' slot order differs from run to run).  Here every draw is independent with probability p_i / sum p, each
+ * stratified draw's marginal without its variance reduction, by content key, WITH replacement. */
+int rl_learn_td_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
+                     int32_t* slots, void* stream);
+/* PERDQNAgent.train_model() for n_learners brains in ONE stream-ordered launch, one workgroup per brain.  rl_learner / rl_replay as for
+ * rl_learn_dueling; kind = RL_PERDQN: fc.0 153->64, fc.2 64->64, fc.4 64->8, ReLU between, 14,536 parameters in state-dict order.
+ *   size gate   size = min(*count, capacity); size <= min_size: no update (the caller passes train_start - 1)
+ *   rows        slots: device int32 [n_learners][n_steps][batch], from rl_learn_td_draw; all are range-checked against [0, size) before
+ *               the first row is fetched: a bad one sets error-flag code 6 and that brain leaves with NONE of its buffers written --
+ *               priority and beta included (the others train)
+ *   each step   beta = min(1, beta + beta_increment) in double; w_i = (float)pow((double)p_i / (double)p_min, -beta) over the batch
+ *               rows' priorities as they stand at this step (written to is_weight when given); target_i = r_i + (1 - done_i) gamma
+ *               max_a Q_target(s'_i); pred_i = Q(s_i)[a_i]; loss = mean(w) * mean((pred - target)^2); Adam exactly as rl_learn_dueling
+ *               makes it; every batch row writes priority[slot] = powf(fabsf(pred - target) + prio_e, prio_a) from this step's
+ *               pre-update values (duplicated slots write equal bits, later steps overwrite earlier ones); loss[s] and
+ *               grad[s][n_params] are written when given
+ *   afterwards  sync_target != 0: target <- params, also below the size gate (PERDQNAgent.learn calls update_target_model() after every
+ *               trigger); state[0] += updates made; state[1] += 1; `packed` is rewritten from the final params, bit for bit what
+ *               rl_policy_pack_weights(RL_PERDQN, ...) makes (split to the nearest f16)
+ * Validation is rl_learn_dueling's with these differences: kind must be RL_PERDQN (anything else: RL_E_UNSUPPORTED naming the kind);
+ * slots == NULL is RL_E_INVALID; priority, seen and beta must not be null; prio_a > 0; batch in [1,64]; at most RL_MAX_CAPTURE_BRAINS
+ * learners.  Deterministic like the other learners: plain f32 FMA, every sum by one thread in a fixed order, no float atomics.
+ * Every older entry point and *_supported answer is unchanged by it (they refuse RL_PERDQN). */
+int rl_learn_td(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
+                const int32_t* slots, void* stream);
 
 /* ---- frames ---------------------------------------------------------------------------------------------------- */
 /* What the painter of Helpers/render.py:51-239 draws, as integers: pixels per cell, the body square (offset, side, border width), the

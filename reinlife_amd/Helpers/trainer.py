@@ -19,7 +19,8 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
             print_results=True, max_agents=100, render=False, static_families=True, training=True, save=True,
             limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None, seed=0, rng=None, per_agent_api=False,
             fused=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
-            learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1):
+            learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
+            learn_td_priority=None):
     """Extra keyword-only arguments: n_worlds / device / seed / rng / synthetic_agents / refill_below (Environment); per_agent_api=True makes the reference's literal
     per-agent get_action / learn calls; fused (default: True for rng="philox" without per_agent_api) runs the loop through
     Environment.run -- whole chunks of ticks per launch, ending where the Tracker closes an interval -- instead of three launches
@@ -50,7 +51,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     batch-wide advantage mean, Adam) as soon as the ring holds 64 rows; the target network is synced in that launch iff a multiple of
     brain.soft_update_freq lies in (last - learn_every, last] (D3QN.py:125-126).  The DQN learners' call is a separate launch and draws
     what it draws without D3QN learners.  The same two deviations apply.  learn_steps: an int is the DQN learners' count; a dict by
-    method name ({"DQN": 5, "D3QN": 1}) sets it per kind.  A name no entry point trains (PERD3QN, PPO, PERDQN), or learn_kinds without
+    method name ({"DQN": 5, "D3QN": 1, "PERDQN": 1}) sets it per kind.  A learn_kinds name no entry point trains (PERD3QN, PPO, PERDQN), or learn_kinds without
     learn="device", is a ValueError before a device is touched.
     learn_prioritized (default None: every run is what it was; True needs learn="device" and at least one Models.PERD3QN, ValueError
     otherwise, before a device is touched; it needs no learn_kinds; the default `learn_every` stays the smallest train_freq of the DQN /
@@ -75,7 +76,21 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     k_epoch (3) full-batch Adam steps on the clipped surrogate plus the smooth-L1 value loss, GAE backwards over the rollout's rows.
     DEVIATIONS: the schedule (once per `learn_every` episodes, not per agent); a rollout is 32 independent draws with replacement, so
     the GAE's neighbours are unrelated rows -- in the reference they are unrelated agents of one tick; all but rollout_steps * 32 of the
-    fresh rows go unused; a chunk that appends more than a ring holds keeps rows by append order."""
+    fresh rows go unused; a chunk that appends more than a ring holds keeps rows by append order.
+    learn_td_priority (default None: every run and every message is what it was; True needs learn="device" and at least one Models.PERDQN,
+    ValueError otherwise, before a device is touched; it needs no learn_kinds; a PERDQN's train_freq sets the default `learn_every` only
+    where PERDQN brains are the only learners): every PERDQN brain trains through rl_learn_td beside a ring of brain.memory_size rows
+    (20,000).  A brains list with a PERDQN runs in the two-launch loop, which captures every tick's transitions into the rings.  After
+    every episode that is a multiple of `learn_every`, behind all the other learners' calls (which stay bit for bit what they are
+    without the keyword), one draw (rl_learn_td_draw, two launches) and ONE rl_learn_td make learn_steps["PERDQN"] (default 1)
+    train_model() updates once the ring holds brain.train_start rows: batch 64, gamma 0.99, lr 1e-3, Adam; model -> target_model at
+    every call.  Three quirks of the reference are reproduced, not repaired: every stored row gets the one priority (0 + 0.01) ** 0.6
+    (append_sample's error is taken against a view of the tensor it has just overwritten); the loss is mean(is_weight) *
+    mean((pred - target)^2), not weighted per row; is_weight = (p_i / min_j p_j) ** -beta over the batch, beta 0.4 -> 1 by 0.001 per
+    update.  DEVIATIONS: the reference's sample() is stratified through its sum tree -- here the 64 draws are independent with
+    probability p_i / sum p, by content key, with replacement; the schedule is per `learn_every` episodes, so brain.epsilon decays
+    once per update made, not once per agent trigger (pass a smaller explore_step for the reference's rate in wall-clock terms).  Until a
+    ring first holds train_start rows each learning call reads its count back (a synchronisation); afterwards none does."""
     if learn == "device" and (per_agent_api or fused is False):
         raise ValueError("trainer(learn='device') needs the fused path (fused=True, per_agent_api=False): the replay rings are filled "
                          "inside the multi-tick launches")
@@ -85,7 +100,8 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
                       limit_reproduction=limit_reproduction, incentivize_killing=incentivize_killing, n_worlds=n_worlds,
                       device=device, seed=seed, rng=rng, synthetic_agents=synthetic_agents, refill_below=refill_below, dist=dist,
                       world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps, learn_kinds=learn_kinds,
-                      learn_prioritized=learn_prioritized, learn_rollout=learn_rollout, rollout_steps=rollout_steps)
+                      learn_prioritized=learn_prioritized, learn_rollout=learn_rollout, rollout_steps=rollout_steps,
+                      learn_td_priority=learn_td_priority)
     env.reset()
     if fused is None:
         fused = env.rng == "philox" and not per_agent_api

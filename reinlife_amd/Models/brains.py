@@ -6,7 +6,8 @@ batched over all agents through Environment.act(), or one state at a time throug
 The per-agent learn() of the reference's brains is accepted and ignored, so that trainer() loops written for the reference keep
 running (a warning is issued once).  DQN brains learn on the device instead, through trainer(learn="device") / learn.DeviceLearner
 (rl_learn), D3QN brains with learn_kinds=("DQN", "D3QN") (rl_learn_dueling) and PERD3QN brains with learn_prioritized=True
-(rl_learn_prioritized, with their prioritised memory); PPO and PERDQN brains stay frozen.
+(rl_learn_prioritized, with their prioritised memory), PPO brains with learn_rollout=True (rl_learn_ppo) and PERDQN brains with
+learn_td_priority=True (rl_learn_td, with the reference's memory and importance weights).
 """
 import random
 import warnings

@@ -158,7 +158,8 @@ class Environment:
                  static_families=True, interactive_results=False, google_colab=False, training=True, save=False,
                  pastel_colors=False, limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None,
                  seed=0, rng=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
-                 learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1):
+                 learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
+                 learn_td_priority=None):
         if not brains:
             raise ValueError("Environment needs a non-empty list of brains")
         if learn not in (None, "device"):
@@ -195,11 +196,20 @@ class Environment:
         if int(rollout_steps) < 1:
             raise ValueError("rollout_steps must be >= 1 (got %r)" % (rollout_steps,))
         self.learn_rollout, self.rollout_steps = bool(learn_rollout), int(rollout_steps)
+        # learn_td_priority=True: every PERDQN brain trains through rl_learn_td on the reference's prioritised memory with importance
+        # weights (PERDQN.py: train_model, Memory).  A keyword of its own, like learn_prioritized.  Checked before a device is touched.
+        if learn_td_priority not in (None, True):
+            raise ValueError("learn_td_priority must be None or True, got %r" % (learn_td_priority,))
+        if learn_td_priority and learn != "device":
+            raise ValueError("learn_td_priority=True needs learn='device' (got learn=%r)" % (learn,))
+        if learn_td_priority and not any(getattr(b, "method", None) == "PERDQN" for b in brains):
+            raise ValueError("learn_td_priority=True needs at least one Models.PERDQN brain (got %s)" % ", ".join(str(getattr(b, "method", b)) for b in brains))
+        self.learn_td_priority = bool(learn_td_priority)
         # learn_steps: minibatch updates per call -- an int is the DQN learners' (as always), a dict by method name sets it per kind;
-        # D3QN defaults to 1 (D3QNAgent.train() makes one update)
-        self.learn_steps_of = {"DQN": 5, "D3QN": 1}
+        # D3QN defaults to 1 (D3QNAgent.train() makes one update), and so does PERDQN (train_model())
+        self.learn_steps_of = {"DQN": 5, "D3QN": 1, "PERDQN": 1}
         if isinstance(learn_steps, dict):
-            bad = [k for k in learn_steps if k not in ENTRY_BY_METHOD]
+            bad = [k for k in learn_steps if k not in ENTRY_BY_METHOD and k != "PERDQN"]
             if bad:
                 raise ValueError("learn_steps: no entry point trains %s brains" % ", ".join(map(str, bad)))
             self.learn_steps_of.update({k: int(v) for k, v in learn_steps.items()})
@@ -295,11 +305,13 @@ class Environment:
             entries = {k: e for k, e in entries.items() if e is not None}
             prio = [k for k, b in enumerate(brains) if self.learn_prioritized and b.method == "PERD3QN"]
             ppo = [k for k, b in enumerate(brains) if self.learn_rollout and b.method == "PPO"]
+            td = [k for k, b in enumerate(brains) if self.learn_td_priority and b.method == "PERDQN"]
             prob = {"with_prob": True} if ppo else {}   # the acting probability of every row (PPO.py:73): only where a PPO brain learns
-            if prio or any(e == "rl_learn_dueling" for e in entries.values()):
-                # a D3QN or prioritised PERD3QN learner's ring holds its brain's `capacity` rows (D3QN.py:62, PERD3QN.py:49, 55: 10,000);
-                # every other ring stays DQN.py:15's
-                self.worlds.enable_capture([int(b.capacity) if (entries.get(k) == "rl_learn_dueling" or k in prio) else BUFFER_LIMIT for k, b in enumerate(brains)], **prob)
+            if prio or td or any(e == "rl_learn_dueling" for e in entries.values()):
+                # a D3QN or prioritised PERD3QN learner's ring holds its brain's `capacity` rows (D3QN.py:62, PERD3QN.py:49, 55: 10,000), a
+                # PERDQN learner's its brain's memory_size (20,000); every other ring stays DQN.py:15's
+                self.worlds.enable_capture([int(b.memory_size) if k in td else int(b.capacity) if (entries.get(k) == "rl_learn_dueling" or k in prio)
+                                            else BUFFER_LIMIT for k, b in enumerate(brains)], **prob)
             else:
                 self.worlds.enable_capture(BUFFER_LIMIT, **prob)
             for k in entries:
@@ -308,19 +320,23 @@ class Environment:
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], prioritized=True)
             for k in ppo:
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], rollout=True)
+            for k in td:
+                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], td_priority=True)
             if not self.learners:
                 raise ValueError("learn='device': none of the brains is of a kind rl_learn trains (DQN)" if self.learn_kinds == ("DQN",) else
                                  "learn='device': none of the brains is of a kind in learn_kinds %r" % (self.learn_kinds,))
             # the default period is the smallest train_freq of the learners a run has WITHOUT learn_prioritized, so that the keyword does
             # not move their schedule; the prioritised learners' own train_freq counts only where they are the only learners -- and
-            # likewise learn_rollout and the PPO learners'
-            timed = ([l for l in self.learners.values() if l.entry not in ("rl_learn_prioritized", "rl_learn_ppo")]
-                     or [l for l in self.learners.values() if l.entry != "rl_learn_ppo"] or list(self.learners.values()))
+            # likewise learn_rollout and the PPO learners', and learn_td_priority and the PERDQN learners'
+            timed = ([l for l in self.learners.values() if l.entry not in ("rl_learn_prioritized", "rl_learn_ppo", "rl_learn_td")]
+                     or [l for l in self.learners.values() if l.entry not in ("rl_learn_ppo", "rl_learn_td")]
+                     or [l for l in self.learners.values() if l.entry != "rl_learn_td"] or list(self.learners.values()))
             self.learn_every = int(learn_every) if learn_every is not None else min(l.train_freq for l in timed)
             frozen = ["%d (%s)" % (k, b.method) for k, b in enumerate(brains) if k not in self.learners]
             if frozen:
                 warn_inference_only(frozen, self.learn_kinds + (("PERD3QN (prioritised)",) if self.learn_prioritized else ())
-                                    + (("PPO (rollouts)",) if self.learn_rollout else ()))
+                                    + (("PPO (rollouts)",) if self.learn_rollout else ())
+                                    + (("PERDQN (TD priorities)",) if self.learn_td_priority else ()))
         elif training:
             warn_inference_only()
 
@@ -626,8 +642,15 @@ class Environment:
                         "drawn by content key with replacement from those appended since the last call, so the GAE's neighbours are unrelated rows "
                         "and the other fresh rows go unused)"
                         % (ppo, self.rollout_steps, sorted({self.learners[k].batch for k in ppo}), sorted({self.learners[k].k_epoch for k in ppo}), self.learn_every))
+        td = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_td")
+        if td:
+            note.append("brains %s trained on the device (rl_learn_td: %d minibatch update(s) of batch %s every %d episodes once the ring holds the "
+                        "brain's train_start rows, loss scaled by the mean importance weight, target synced at every call, rows drawn with "
+                        "probability priority / sum by content key with replacement -- independent draws, not the reference's stratified ones; "
+                        "every new row gets the reference's one priority (0 + 0.01) ** 0.6; epsilon decays once per update)"
+                        % (td, self.learn_steps_of["PERDQN"], sorted({self.learners[k].batch for k in td}), self.learn_every))
         if frozen:
-            note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if (duel or prio or ppo) else
+            note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if (duel or prio or ppo or td) else
                         "brains %s as loaded / initialised (their kinds do not learn in this build)" % frozen)
         return "; ".join(note)
 
@@ -643,7 +666,13 @@ class Environment:
         and one rl_learn_prioritized, ONE update per call as PERD3QNAgent.train() makes.
         PPO learners (learn_rollout=True) come last, behind those calls, which again stay what they are without them: one on-policy draw
         (DeviceWorlds.draw_rollout, two launches) and one rl_learn_ppo of `rollout_steps` rollouts (PPO.learn(), PPO.py:136-162), on
-        every call -- PPO has no exploration gate; a window without fresh rows makes no update."""
+        every call -- PPO has no exploration gate; a window without fresh rows makes no update.
+        PERDQN learners (learn_td_priority=True) come behind the PPO call, and all earlier calls stay what they are without them: one draw
+        (DeviceWorlds.draw_td, two launches) and one rl_learn_td of learn_steps["PERDQN"] (1) updates, on every call -- the reference has no
+        exploration gate; below brain.train_start rows the call only copies model -> target_model (PERDQNAgent.learn).  train_model()'s
+        epsilon decay follows on the host: once per update made.  Whether a call trained depends on the ring's count, which lives on the
+        device: it is read back once per call until it first reaches train_start (it never falls again) -- these early calls SYNCHRONISE
+        with the device; later ones do not."""
         dqn = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn"]
         if dqn:
             self.worlds.learn(dqn, self.learn_steps, slots=self.worlds.draw_slots(dqn, self.learn_steps))
@@ -667,6 +696,18 @@ class Environment:
         ppo = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_ppo"]
         if ppo:
             self.worlds.learn(ppo, self.rollout_steps, slots=self.worlds.draw_rollout(ppo, self.rollout_steps))
+        td = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_td"]
+        n = self.learn_steps_of["PERDQN"]
+        for batch in sorted({l.batch for l in td}):
+            ls = [l for l in td if l.batch == batch]
+            self.worlds.learn(ls, n, slots=self.worlds.draw_td(ls, n))
+            for l in ls:
+                if not l.trained_from:   # (a read-back: only until the ring first holds train_start rows)
+                    l.trained_from = min(int(l.ring["count"].item()), int(l.ring["state"].shape[0])) >= l.train_start
+                if l.trained_from:       # train_model(): epsilon loses epsilon_decay at the start of every update while above epsilon_min
+                    for _ in range(n):
+                        if l.brain.epsilon > l.brain.epsilon_min:
+                            l.brain.epsilon -= l.brain.epsilon_decay
 
     def sync_learners(self):
         """The trained parameters into the brains' modules (DeviceLearner.sync_to_module): what Saver and state_dict() read."""

@@ -78,9 +78,15 @@ class Ppo(C.Structure):  # rl_ppo
     _fields_ = [("lmbda", C.c_float), ("eps_clip", C.c_float), ("k_epoch", C.c_int32)] + [(n, C.c_void_p) for n in ("seen", "fresh", "keys")]
 
 
+class TdPrio(C.Structure):  # rl_tdprio
+    _fields_ = ([(n, C.c_void_p) for n in ("priority", "keys", "seen", "beta")] + [(n, C.c_float) for n in ("p_new", "prio_e", "prio_a")]
+                + [("beta_increment", C.c_double), ("is_weight", C.c_void_p)])
+
+
 SITE_LEARN = 10          # RL_SITE_LEARN: the Philox site of rl_learn's minibatch draws
 SITE_LEARN_PRIO = 11     # RL_SITE_LEARN_PRIO: the Philox site of rl_learn_prioritized_draw's draws
 SITE_LEARN_ROLLOUT = 12  # RL_SITE_LEARN_ROLLOUT: the Philox site of rl_learn_rollout's draws
+SITE_LEARN_TD = 13       # RL_SITE_LEARN_TD: the Philox site of rl_learn_td_draw's draws
 MAX_CAPTURE_BRAINS = 16  # RL_MAX_CAPTURE_BRAINS
 PPO_ROLLOUT_MAX = 32     # RL_PPO_ROLLOUT_MAX: the rows of a rollout at most (rl_learn_ppo)
 
@@ -131,6 +137,9 @@ ABI = [
     ("rl_learn_ppo_supported", C.c_int, [C.c_int]),
     ("rl_learn_ppo", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Ppo), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_rollout", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Ppo), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_td_supported", C.c_int, [C.c_int]),
+    ("rl_learn_td_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_td", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),
     ("rl_render", C.c_int, [_P, C.POINTER(RenderStyle), _P, C.c_int, _P, _P]),
     ("rl_set_option", C.c_int, [C.c_char_p, C.c_char_p]),
     ("rl_get_option", C.c_int, [_P, C.c_char_p]),

@@ -7,7 +7,7 @@
 
 #include "rl_common.h"
 
-// implemented in rl_world.hip / rl_policy.hip / rl_render.hip / rl_learn.hip / rl_learn_dueling.hip / rl_learn_prio.hip
+// implemented in rl_world.hip / rl_policy.hip / rl_render.hip / rl_learn.hip / rl_learn_dueling.hip / rl_learn_prio.hip / rl_learn_td.hip
 size_t rl_world_smem_bytes(int cpad, int cap, int hash, int plane_stride, int height);
 int rl_world_block();
 int rl_world_launch_step(rl_world*, const int8_t*, const rl_tape*, const rl_step_out*, hipStream_t);
@@ -35,6 +35,9 @@ int rl_learn_dueling_launch(rl_world*, const rl_learner*, const rl_replay*, int,
 int rl_learn_prioritized_supported_impl(int);
 int rl_learn_prioritized_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_prio*, int, int, const int32_t*, hipStream_t);
 int rl_learn_prioritized_draw_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_prio*, int, int, int32_t*, hipStream_t);
+int rl_learn_td_supported_impl(int);
+int rl_learn_td_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_tdprio*, int, int, const int32_t*, hipStream_t);
+int rl_learn_td_draw_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_tdprio*, int, int, int32_t*, hipStream_t);
 int rl_learn_ppo_supported_impl(int);
 int rl_learn_ppo_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, const int32_t*, hipStream_t);
 int rl_learn_rollout_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, int32_t*, hipStream_t);
@@ -580,6 +583,61 @@ int rl_render(rl_world* h, const rl_render_style* style, const int32_t* worlds, 
         return RL_E_INVALID;
     }
     return rl_render_launch(h, style, worlds, n_frames, frames, (hipStream_t)stream);
+}
+
+int rl_learn_td_supported(int kind) { return rl_learn_td_supported_impl(kind); }
+
+// what rl_learn_td and rl_learn_td_draw ask of their common arguments (`draw`: the draw also needs the rings' age column and the keys
+// scratch of rl_tdprio; the update needs the learner's buffers and beta)
+static int check_td(const char* who, bool draw, rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds,
+                    int n_learners, int n_steps, const void* slots)
+{
+    if (!h) { rl_set_error("%s: null handle", who); return RL_E_INVALID; }
+    if (!learners || !rings || !tds) { rl_set_error("%s: null learners / rings / tds", who); return RL_E_INVALID; }
+    if (n_learners < 1 || n_learners > RL_MAX_CAPTURE_BRAINS) { rl_set_error("%s: n_learners must be in [1,%d] (got %d)", who, RL_MAX_CAPTURE_BRAINS, n_learners); return RL_E_INVALID; }
+    if (n_steps < 1) { rl_set_error("%s: n_steps must be >= 1 (got %d)", who, n_steps); return RL_E_INVALID; }
+    if (!slots) {
+        rl_set_error(draw ? "%s: slots must not be null" : "%s: slots must not be null -- the minibatches of a prioritised memory are drawn by rl_learn_td_draw", who);
+        return RL_E_INVALID;
+    }
+    for (int i = 0; i < n_learners; ++i) {
+        const rl_learner& l = learners[i];
+        const rl_replay& r = rings[i];
+        const rl_tdprio& p = tds[i];
+        if (!rl_learn_td_supported_impl(l.kind)) { rl_set_error("%s: learner %d has brain kind %d; this entry point trains RL_PERDQN (4) only (rl_learn_td_supported)", who, i, l.kind); return RL_E_UNSUPPORTED; }
+        if (draw) {
+            if (!l.state) { rl_set_error("%s: learner %d: state must not be null", who, i); return RL_E_INVALID; }
+        } else if (!l.params || !l.target || !l.adam_m || !l.adam_v || !l.state || !l.packed) {
+            rl_set_error("%s: learner %d: params / target / adam_m / adam_v / state / packed must not be null", who, i); return RL_E_INVALID;
+        }
+        if (l.batch < 1 || l.batch > 64) { rl_set_error("%s: learner %d: batch must be in [1,64] (got %d)", who, i, l.batch); return RL_E_INVALID; }
+        if (!r.state || !r.state_prime || !r.action || !r.reward || !r.done || !r.count || (draw && !r.age) || r.capacity < 1 || r.capacity > 0x7fffffff) {
+            rl_set_error("%s: replay %d incomplete (state / state_prime / action / reward / done / %scount, capacity in [1, 2^31))", who, i, draw ? "age / " : ""); return RL_E_INVALID;
+        }
+        if (draw) {
+            if (!p.priority || !p.keys || !p.seen) { rl_set_error("%s: td %d: priority / keys / seen must not be null", who, i); return RL_E_INVALID; }
+        } else {
+            if (!p.priority || !p.seen || !p.beta) { rl_set_error("%s: td %d: priority / seen / beta must not be null", who, i); return RL_E_INVALID; }
+            if (!(p.prio_a > 0.0f)) { rl_set_error("%s: td %d: prio_a must be > 0 (got %g)", who, i, (double)p.prio_a); return RL_E_INVALID; }
+        }
+    }
+    return RL_OK;
+}
+
+int rl_learn_td_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
+                     int32_t* slots, void* stream)
+{
+    if (int rc = check_td("rl_learn_td_draw", true, h, learners, rings, tds, n_learners, n_steps, slots)) return rc;
+    DeviceGuard guard(device_of_pointer(slots));
+    return rl_learn_td_draw_launch(h, learners, rings, tds, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+int rl_learn_td(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
+                const int32_t* slots, void* stream)
+{
+    if (int rc = check_td("rl_learn_td", false, h, learners, rings, tds, n_learners, n_steps, slots)) return rc;
+    DeviceGuard guard(device_of_pointer(learners[0].params));
+    return rl_learn_td_launch(h, learners, rings, tds, n_learners, n_steps, slots, (hipStream_t)stream);
 }
 
 void rl_philox(uint64_t seed, uint32_t epoch, uint32_t world, uint32_t tick, uint32_t site, uint32_t index, uint32_t out[4])

@@ -1,5 +1,6 @@
-// rl_learn_dev.h -- what the learning units (rl_learn.hip: k_learn_dqn, rl_learn_dueling.hip: k_learn_d3qn, rl_learn_prio.hip: the prioritised draw) share: torch's Adam update
-// of one parameter, the toward-zero f16 split of rl_policy.hip's host packer on the device, the packed layouts' index rule, the
+// rl_learn_dev.h -- what the learning units (rl_learn.hip: k_learn_dqn, rl_learn_dueling.hip: k_learn_d3qn, rl_learn_prio.hip: the prioritised draws,
+// rl_learn_td.hip: k_learn_perdqn) share: torch's Adam update of one parameter, the toward-zero f16 split of rl_policy.hip's host packer on the
+// device and its to-nearest counterpart (PERDQN), the packed layouts' index rule, the
 // content key of a ring row and the decimal a float hyperparameter stands for.  Everything is inline in an unnamed namespace: each unit gets its own copy.
 #pragma once
 #include "rl_policy_dev.h"
@@ -56,6 +57,32 @@ __device__ inline void learn_store_fragment(const float (&x)[8], uint4* hi_dst, 
     for (int e = 0; e < 8; ++e) {
         hi[e] = learn_f16_rtz(x[e]);
         lo[e] = learn_f16_rtz(x[e] - learn_f16_to_float(hi[e]));   // (the subtraction is exact)
+    }
+    *hi_dst = uint4{hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16)};
+    *lo_dst = uint4{lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16)};
+}
+// ---- ... and the split to the NEAREST f16, ties to even (f16_rne, split2_host with rne: PERDQN's packed weights alone) ----
+__device__ inline uint32_t learn_f16_rne(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    const uint32_t sign = (u >> 16) & 0x8000u;
+    const int e = (int)((u >> 23) & 0xff) - 127;
+    if (e < -25) return sign;                                         // below half the smallest subnormal
+    const int eq = e < -14 ? -14 : e;                                 // exponent of the f16 quantum 2^(eq - 10)
+    const int shift = 13 + (eq - e);
+    const uint32_t man = (u & 0x7fffffu) | 0x800000u;
+    uint32_t r = man >> shift;
+    const uint32_t rem = man & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    if (rem > half || (rem == half && (r & 1u))) ++r;                 // (a carry into the exponent is the right result)
+    return sign | (uint32_t)(((eq + 14) << 10) + r);
+}
+__device__ inline void learn_store_fragment_rne(const float (&x)[8], uint4* hi_dst, uint4* lo_dst)
+{
+    uint32_t hi[8], lo[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        hi[e] = learn_f16_rne(x[e]);
+        lo[e] = learn_f16_rne(x[e] - learn_f16_to_float(hi[e]));   // (the subtraction is exact)
     }
     *hi_dst = uint4{hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16)};
     *lo_dst = uint4{lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16)};

@@ -29,7 +29,9 @@
 
 namespace {
 
-constexpr int kPrioSite = RL_SITE_LEARN_PRIO;
+// The same two kernels serve the PERDQN memory (rl_learn_td_draw, TD = true; PERDQN.py's Memory / SumTree): its new rows are stamped with
+// a constant (rl_tdprio.p_new: append_sample's priority is (0 + e) ** a whatever the row, rl_learn_td.hip), and the race weight is the
+// stored priority itself, which already carries ** a -- no powf, no weight column.  Salts from RL_SITE_LEARN_TD.
 
 struct PrioBrain {
     const float *r_state, *r_state_prime, *r_reward;
@@ -40,7 +42,8 @@ struct PrioBrain {
     long long r_capacity;
     float *priority, *weight;
     unsigned long long* keys;
-    const float* prio_max;
+    const float* prio_max;       // (TD: null)
+    float p_new;                 // (TD only)
     unsigned long long* seen;
     const long long* state;      // rl_learner.state ([1] = calls made)
     float alpha;
@@ -53,7 +56,8 @@ struct PrioArgs {
     int n_steps;
 };
 
-// one wave per ring row: the stamp, weight[row] = priority[row]^alpha, keys[row]
+// one wave per ring row: the stamp, weight[row] = priority[row]^alpha (TD: none), keys[row]
+template <bool TD>
 __global__ __launch_bounds__(256) void k_prio_prepare(const PrioArgs A)
 {
     const PrioBrain& B = A.b[blockIdx.y];
@@ -66,10 +70,15 @@ __global__ __launch_bounds__(256) void k_prio_prepare(const PrioArgs A)
     if (lane == 0) {
         const unsigned long long fresh = count > seen ? count - seen : 0ull;          // rows appended since the last draw
         const unsigned long long behind = ((unsigned long long)row + cap - seen % cap) % cap;   // slots from seen's to this row's, going round
-        float p;
-        if (fresh >= cap || behind < fresh) { p = *B.prio_max; B.priority[row] = p; }
-        else p = B.priority[row];
-        B.weight[row] = powf(p, B.alpha);
+        const bool stamp = fresh >= cap || behind < fresh;
+        if (TD) {
+            if (stamp) B.priority[row] = B.p_new;
+        } else {
+            float p;
+            if (stamp) { p = *B.prio_max; B.priority[row] = p; }
+            else p = B.priority[row];
+            B.weight[row] = powf(p, B.alpha);
+        }
         B.keys[row] = k;
     }
 }
@@ -80,6 +89,7 @@ __device__ inline bool prio_less(float t, uint64_t v, int i, float bt, uint64_t 
 }
 
 // one workgroup per draw: slots[brain][d] = the row with the smallest (t, v, slot)
+template <bool TD>
 __global__ __launch_bounds__(256) void k_prio_pick(const PrioArgs A)
 {
     __shared__ float best_t[256];
@@ -91,14 +101,14 @@ __global__ __launch_bounds__(256) void k_prio_pick(const PrioArgs A)
     const unsigned long long count = *B.r_count;
     const long long size = count < (unsigned long long)B.r_capacity ? (long long)count : B.r_capacity;
     if (d == 0 && tid == 0) *B.seen = count;   // (k_prio_prepare, the only reader, is the launch in front of this one)
-    const rl_u4 r = rl_philox4x32(A.seed, 0u, (uint32_t)brain, (uint32_t)B.state[1], (uint32_t)kPrioSite, (uint32_t)d);
+    const rl_u4 r = rl_philox4x32(A.seed, 0u, (uint32_t)brain, (uint32_t)B.state[1], (uint32_t)(TD ? RL_SITE_LEARN_TD : RL_SITE_LEARN_PRIO), (uint32_t)d);
     const uint64_t salt = ((uint64_t)r.y << 32) | r.x;
     float bt = INFINITY;
     uint64_t bv = ~0ull;
     int bi = 0x7fffffff;
     for (long long i = tid; i < size; i += 256) {
         const uint64_t v = learn_mix64(B.keys[i] ^ salt);
-        const float w = B.weight[i];
+        const float w = TD ? B.priority[i] : B.weight[i];
         const float u = ((float)(uint32_t)(v >> 41) + 0.5f) * (1.0f / 8388608.0f);   // exact: 24 significant bits, in [2^-24, 1 - 2^-24]
         const float t = w > 0.0f ? -logf(u) / w : INFINITY;                         // (a NaN weight: +inf too)
         if (prio_less(t, v, (int)i, bt, bv, bi)) { bt = t; bv = v; bi = (int)i; }
@@ -120,29 +130,42 @@ __global__ __launch_bounds__(256) void k_prio_pick(const PrioArgs A)
 
 }  // namespace
 
-int rl_learn_prioritized_draw_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners,
-                                     int n_steps, int32_t* slots, hipStream_t stream)
+template <bool TD>
+static int prio_draw_launch(const char* who, rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, const rl_tdprio* tds,
+                            int n_learners, int n_steps, int32_t* slots, hipStream_t stream)
 {
     PrioArgs a{};
     long long max_cap = 1;
     int max_batch = 1;
     for (int i = 0; i < n_learners; ++i) {
         const rl_replay& r = rings[i];
-        const rl_prio& p = prios[i];
         PrioBrain& b = a.b[i];
         b.r_state = r.state; b.r_state_prime = r.state_prime; b.r_reward = r.reward; b.r_action = r.action; b.r_done = r.done; b.r_age = r.age;
         b.r_count = r.count; b.r_capacity = r.capacity;
-        b.priority = p.priority; b.weight = p.weight; b.keys = p.keys; b.prio_max = p.prio_max; b.seen = p.seen; b.alpha = p.alpha;
+        if (TD) { b.priority = tds[i].priority; b.keys = tds[i].keys; b.seen = tds[i].seen; b.p_new = tds[i].p_new; }
+        else { const rl_prio& p = prios[i]; b.priority = p.priority; b.weight = p.weight; b.keys = p.keys; b.prio_max = p.prio_max; b.seen = p.seen; b.alpha = p.alpha; }
         b.state = (const long long*)learners[i].state; b.batch = learners[i].batch;
         max_cap = r.capacity > max_cap ? r.capacity : max_cap;
         max_batch = b.batch > max_batch ? b.batch : max_batch;
     }
     a.slots = slots; a.seed = h->cfg.seed; a.n_steps = n_steps;
-    hipLaunchKernelGGL(k_prio_prepare, dim3((unsigned)((max_cap + 3) / 4), n_learners), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(k_prio_prepare<TD>, dim3((unsigned)((max_cap + 3) / 4), n_learners), dim3(256), 0, stream, a);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rl_set_error("rl_learn_prioritized_draw: launch of the prepare kernel failed: %s", hipGetErrorString(e)); return RL_E_LAUNCH; }
-    hipLaunchKernelGGL(k_prio_pick, dim3(n_steps * max_batch, n_learners), dim3(256), 0, stream, a);
+    if (e != hipSuccess) { rl_set_error("%s: launch of the prepare kernel failed: %s", who, hipGetErrorString(e)); return RL_E_LAUNCH; }
+    hipLaunchKernelGGL(k_prio_pick<TD>, dim3(n_steps * max_batch, n_learners), dim3(256), 0, stream, a);
     e = hipGetLastError();
-    if (e != hipSuccess) { rl_set_error("rl_learn_prioritized_draw: launch of the pick kernel failed: %s", hipGetErrorString(e)); return RL_E_LAUNCH; }
+    if (e != hipSuccess) { rl_set_error("%s: launch of the pick kernel failed: %s", who, hipGetErrorString(e)); return RL_E_LAUNCH; }
     return RL_OK;
+}
+
+int rl_learn_prioritized_draw_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners,
+                                     int n_steps, int32_t* slots, hipStream_t stream)
+{
+    return prio_draw_launch<false>("rl_learn_prioritized_draw", h, learners, rings, prios, nullptr, n_learners, n_steps, slots, stream);
+}
+
+int rl_learn_td_draw_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners,
+                            int n_steps, int32_t* slots, hipStream_t stream)
+{
+    return prio_draw_launch<true>("rl_learn_td_draw", h, learners, rings, nullptr, tds, n_learners, n_steps, slots, stream);
 }

@@ -1,5 +1,5 @@
-"""DeviceLearner: what a DQN, D3QN or (prioritized=True) PERD3QN brain needs to learn on the device (rl_learn / rl_learn_dueling /
-rl_learn_prioritized, include/reinlife_hip.h; PPO and PERDQN brains stay frozen) -- the flat f32 master parameters,
+"""DeviceLearner: what a DQN, D3QN, (prioritized=True) PERD3QN, (rollout=True) PPO or (td_priority=True) PERDQN brain needs to learn on
+the device (rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo / rl_learn_td, include/reinlife_hip.h) -- the flat f32 master parameters,
 the target network, Adam's moments, the step / call counters and the packed weights the acting kernels read, all as device tensors.
 
 Reference: DQNAgent owns `agent`, `target`, `memory` and `optimizer` (ReinLife/Models/DQN.py:48-52); train() (DQN.py:80-83, 142-153)
@@ -30,7 +30,19 @@ carry the acting probability (enable_capture(..., with_prob=True)) -- the bookke
 rollout, the rows the last window held, and the draw's scratch keys (DeviceWorlds.draw_rollout: `batch` = 32 rows per rollout, drawn
 uniformly with replacement by content key from the rows appended since the last call).  Deviations: the schedule is the caller's; a rollout
 is 32 independent draws, so the GAE recursion's neighbours are unrelated rows (in the reference: unrelated agents of one tick); the fresh
-rows not drawn go unused."""
+rows not drawn go unused.
+
+PERDQNAgent (ReinLife/Models/PERDQN.py) owns `model`, `target_model`, `memory` (a sum tree of priorities) and `optimizer`; train_model()
+makes one Adam step on a minibatch of 64 drawn by priority.  DeviceLearner(brain, device, ring, td_priority=True) is that agent's learner
+(rl_learn_td): lr, gamma, batch, train_start, train_freq and the memory's size from the brain; beside the D3QN learner's tensors the
+memory's priorities (one per ring row), the ring count as of the last draw, the draw's scratch keys and beta (a device double, 0.4 -> 1 by
+0.001 per update).  Three quirks of the reference are reproduced, not repaired: append_sample gives EVERY new row the priority
+(0 + 0.01) ** 0.6 (its error is taken against a view of the tensor it has just overwritten; `p_new` is that float32, made with torch as
+the reference makes it); the loss is mean(is_weight) * mean((pred - target)^2), not weighted per row; is_weight is
+(p_i / min_j p_j) ** -beta over the batch.  learn() copies model -> target_model after every trigger, so sync_target is always on.
+Deviations: Memory.sample is stratified through the sum tree -- here every draw is independent with probability p_i / sum p, by content
+key, with replacement (DeviceWorlds.draw_td); the schedule is the caller's (once per `learn_every` episodes), so epsilon decays once per
+update made, not once per agent trigger -- a smaller explore_step restores the reference's rate in wall-clock terms."""
 import copy
 import ctypes as C
 
@@ -50,9 +62,14 @@ def entry_of(kind):
 
 
 class DeviceLearner:
-    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False):
+    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False, td_priority=False):
         lib = _lib.lib()
-        if rollout:   # an explicit opt-in, like prioritized: entry_of() and ENTRY_BY_METHOD keep answering what they answered
+        if td_priority:   # an explicit opt-in, like prioritized and rollout: entry_of() and ENTRY_BY_METHOD keep answering what they answered
+            if prioritized or rollout or not lib.rl_learn_td_supported(brain.kind):
+                raise ValueError("td_priority=True is for PERDQN brains (rl_learn_td); got a %s brain (kind %d)%s"
+                                 % (brain.method, brain.kind, " with prioritized=True" if prioritized else " with rollout=True" if rollout else ""))
+            self.entry = "rl_learn_td"
+        elif rollout:   # an explicit opt-in, like prioritized: entry_of() and ENTRY_BY_METHOD keep answering what they answered
             if prioritized or not lib.rl_learn_ppo_supported(brain.kind):
                 raise ValueError("rollout=True is for PPO brains (rl_learn_ppo); got a %s brain (kind %d)%s"
                                  % (brain.method, brain.kind, " with prioritized=True" if prioritized else ""))
@@ -83,6 +100,13 @@ class DeviceLearner:
             self.batch, self.min_size = _lib.PPO_ROLLOUT_MAX, 0  # the rows of a rollout; no size gate (an empty window makes no update)
             self.n_steps_default = 1                             # one PPO.learn() per call
             self.sync_target = False
+        elif self.entry == "rl_learn_td":   # PERDQNAgent.__init__: the brain's own hyperparameters
+            self.lr, self.gamma = float(getattr(brain, "learning_rate", 1e-3)), float(getattr(brain, "discount_factor", 0.99))
+            self.batch = int(getattr(brain, "batch_size", 64))
+            self.train_start, self.memory_size = int(getattr(brain, "train_start", 1000)), int(getattr(brain, "memory_size", 20000))
+            self.min_size = self.train_start - 1                 # learn(): n_entries >= train_start
+            self.n_steps_default = 1                             # train_model() makes one update
+            self.sync_target = True                              # learn(): update_target_model() after every trigger
         elif self.entry == "rl_learn":
             self.lr = float(getattr(brain, "learning_rate", 0.0005))
             self.gamma, self.batch, self.min_size = GAMMA, BATCH, MIN_SIZE
@@ -105,6 +129,13 @@ class DeviceLearner:
         self.fresh = None         # rollout=True: the window's bookkeeping (seen and keys above, fresh here)
         if rollout and ring is not None:
             self._make_ppo()
+        self.prio_e, self.prio_a, self.beta_increment = 0.01, 0.6, 0.001   # Memory.e, Memory.a, Memory.beta_increment_per_sampling
+        self.p_new = float((torch.zeros(()) + self.prio_e) ** self.prio_a)  # append_sample's priority: float32 (0 + e) ** a, as torch makes it
+        self.beta_is = None       # td_priority=True: Memory.beta, a device double
+        self.is_weight = None     # optional device float32 [n_steps, batch]: rl_learn_td's importance weights (tests, diagnostics)
+        self.trained_from = False  # td_priority=True: the ring has reached train_start (Environment.learn_now reads it back until then)
+        if td_priority and ring is not None:
+            self._make_td()
         self.loss = None          # optional device float32 [n_steps]
         self.grad = None          # optional device float32 [n_steps, n_params] (tests, diagnostics)
 
@@ -141,6 +172,25 @@ class DeviceLearner:
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         return _lib.Prio(p(self.priority), p(self.weight), p(self.keys), p(self.prio_max), p(self.seen), self.alpha)
 
+    def _make_td(self):
+        """The PERDQN memory beside the ring (rl_tdprio), sized to it: no priorities yet, nothing seen, beta 0.4 (Memory.beta)."""
+        capacity = int(self.ring["state"].shape[0])
+        self.priority = torch.zeros(capacity, dtype=torch.float32, device=self.device)
+        self.keys = torch.zeros(capacity, dtype=torch.int64, device=self.device)
+        self.seen = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.beta_is = torch.full((1,), 0.4, dtype=torch.float64, device=self.device)
+
+    def td_struct(self):
+        if self.entry != "rl_learn_td":
+            raise _lib.ReinLifeHipError("this DeviceLearner has no PERDQN memory (DeviceLearner(..., td_priority=True))")
+        if self.ring is None:
+            raise _lib.ReinLifeHipError("this DeviceLearner has no replay ring (DeviceLearner.ring)")
+        if self.priority is None or self.priority.numel() != self.ring["state"].shape[0]:
+            self._make_td()
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        return _lib.TdPrio(p(self.priority), p(self.keys), p(self.seen), p(self.beta_is), self.p_new, self.prio_e, self.prio_a,
+                           self.beta_increment, p(self.is_weight))
+
     def _make_ppo(self):
         """The on-policy window's bookkeeping beside the ring (rl_ppo), sized to it: nothing seen, no fresh rows."""
         capacity = int(self.ring["state"].shape[0])
@@ -175,9 +225,14 @@ class DeviceLearner:
 
     def sync_to_module(self):
         """The trained parameters into brain.agent and the target network's into brain.target (made on first use: a copy, no
-        generator draw), so that Saver and state_dict() see them.  D3QN and PERD3QN: into brain.eval_net and brain.target_net."""
+        generator draw), so that Saver and state_dict() see them.  D3QN and PERD3QN: into brain.eval_net and brain.target_net; PERDQN: into
+        brain.model and brain.target_model."""
         if self.entry == "rl_learn_ppo":   # PPO.py:46: one module, no target
             self._load(self.brain.model, self.params.cpu().numpy())
+            return
+        if self.entry == "rl_learn_td":    # PERDQNAgent: model and target_model (Saver reads model)
+            self._load(self.brain.model, self.params.cpu().numpy())
+            self._load(self.brain.target_model, self.target.cpu().numpy())
             return
         if self.entry in ("rl_learn_dueling", "rl_learn_prioritized"):
             self._load(self.brain.eval_net, self.params.cpu().numpy())

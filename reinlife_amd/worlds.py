@@ -487,6 +487,27 @@ class DeviceWorlds:
         self.launches += 2
         return slots
 
+    def draw_td(self, learners, n_steps):
+        """The minibatches of PERDQN learners (DeviceLearner(..., td_priority=True)) for learn(learners, n_steps, slots=...): the draw of
+        the reference's Memory on the device (rl_learn_td_draw) -- first every row appended since the last draw gets the one priority
+        append_sample gives (learner.p_new), then each draw takes a row with probability priority / sum, with replacement, by a key of the
+        rows' content: the same rows whatever slots they sit in (the reference's sample() is stratified through its sum tree; here the
+        draws are independent).  Device int32 [len(learners), n_steps, batch], queued on the current stream."""
+        n = len(learners)
+        if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
+            raise ValueError("draw_td(): 1 to %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
+        if len({l.batch for l in learners}) != 1:
+            raise ValueError("draw_td(): the learners of a call must share one batch size")
+        if any(l.entry != "rl_learn_td" for l in learners):
+            raise ValueError("draw_td(): every learner must be a PERDQN one (DeviceLearner(..., td_priority=True))")
+        arr = (_lib.Learner * n)(*[l.struct() for l in learners])
+        rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
+        tds = (_lib.TdPrio * n)(*[l.td_struct() for l in learners])
+        slots = torch.zeros((n, int(n_steps), int(learners[0].batch)), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.rl_learn_td_draw(self.handle, arr, rings, tds, n, int(n_steps), _ptr(slots), self._stream()), "rl_learn_td_draw")
+        self.launches += 2
+        return slots
+
     def learn(self, learners, n_steps, slots=None, gate=True):
         """DQNAgent.train() (DQN.py:80-83, 142-153) for every DeviceLearner of `learners` in ONE launch (rl_learn), queued on the current
         stream behind the ticks launched so far: `n_steps` minibatch updates per brain on its replay ring (learner.ring), then the
@@ -498,7 +519,9 @@ class DeviceWorlds:
         only when learner.sync_target says so), a list of prioritised PERD3QN learners to rl_learn_prioritized (PERD3QNAgent.train(),
         PERD3QN.py:94-115: the same update, and the batch rows' priorities rewritten; `slots` must come from draw_prioritized()), a list of
         PPO learners to rl_learn_ppo (PPO.learn(), PPO.py:136-162: n_steps rollouts of `batch` rows, k_epoch Adam steps each; `slots` from
-        draw_rollout(), or the caller's own rows with gate=False, which leaves the empty-window gate out).  The
+        draw_rollout(), or the caller's own rows with gate=False, which leaves the empty-window gate out), a list of PERDQN learners to
+        rl_learn_td (PERDQNAgent.train_model(): the loss scaled by the mean importance weight, the batch rows' priorities rewritten;
+        `slots` from draw_td()).  The
         learners of one call must all belong to one entry point: ValueError otherwise."""
         if not learners:
             return
@@ -520,6 +543,9 @@ class DeviceWorlds:
         if entry == "rl_learn_prioritized":
             prios = (_lib.Prio * n)(*[l.prio_struct() for l in learners])
             _lib.check(self.lib.rl_learn_prioritized(self.handle, arr, rings, prios, n, int(n_steps), _ptr(slots), self._stream()), entry)
+        elif entry == "rl_learn_td":
+            tds = (_lib.TdPrio * n)(*[l.td_struct() for l in learners])
+            _lib.check(self.lib.rl_learn_td(self.handle, arr, rings, tds, n, int(n_steps), _ptr(slots), self._stream()), entry)
         elif entry == "rl_learn_ppo":
             ppos = (_lib.Ppo * n)(*[l.ppo_struct(gate=gate) for l in learners])
             _lib.check(self.lib.rl_learn_ppo(self.handle, arr, rings, ppos, n, int(n_steps), _ptr(slots), self._stream()), entry)
