@@ -559,6 +559,38 @@ int rl_learn_td_draw(rl_world* h, const rl_learner* learners, const rl_replay* r
 int rl_learn_td(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
                 const int32_t* slots, void* stream);
 
+/* ---- learning on several ranks: one merge of the learners per learning episode ------------------------------------- */
+/* THIS BUILD'S OWN -- the reference has no multi-process training.  Every rank trains its learners on its own rings exactly as a single
+ * rank does; at the end of a learning episode the ranks export their learners into one row each, all-gather the rows (the caller's
+ * collective) and merge: periodic PARAMETER averaging, not gradient averaging.  Memory-side state (rings, priorities, windows, beta,
+ * state[1]) stays rank-local.
+ * The floats of one rank's row segment for a learner of `kind`: 3 * rl_policy_n_params(kind) + 2, laid out params | adam_m | adam_v |
+ * state[0], the step count as two 32-bit words, low then high, in the bytes of two floats (3 * 53,897 is odd: nothing may assume 8-byte
+ * alignment).  -1 for an unknown kind. */
+int64_t rl_learn_merge_floats(int kind);
+/* ONE launch: learner i's segment, which starts at the sum of the earlier learners' rl_learn_merge_floats, is filled from its buffers
+ * (params, adam_m, adam_v, state; target and packed are not read and may be NULL).  row: device, at least the sum of all segments. */
+int rl_learn_export(rl_world* h, const rl_learner* learners, int n_learners, float* row, void* stream);
+/* The merge.  rows: device [n_ranks][row_stride_floats], as an all-gather of the exported rows lays them out; it must not overlap a
+ * learner's buffer.  Per learner, with s_r the step count of rank r's row:
+ *   participants  the ranks with s_r == max_r s_r (all of them when the counts are equal, which covers "nobody trained"); decided on
+ *                 the device from the rows' step words, no read-back
+ *   the mean      every element of params, adam_m and adam_v becomes the participants' mean: summed in rank order in double (from
+ *                 -0.0, the additive identity), divided by their number in double, rounded to float ONCE -- the same bits on every
+ *                 rank, in every run, whatever else is in the launch; one participant: its values, bit for bit
+ *   state         state[0] <- max_r s_r (a rank that is behind adopts the result); state[1] is untouched
+ *   target        sync_target != 0: target <- the merged params; otherwise left alone.  RL_PPO: target may be NULL
+ *   packed        rewritten from the merged params, bit for bit what rl_policy_pack_weights(kind, ...) makes of them
+ * Kinds may be mixed within a call (n_learners in [1, RL_MAX_CAPTURE_BRAINS], n_ranks in [1, 64]); of rl_learner only kind, the six
+ * buffers and sync_target are read.  Two launches (mean, pack), stream-ordered, no allocation, no host read-back.  Validated on the host
+ * before anything is launched: a null buffer, a bad count or a stride shorter than the learners' segments is RL_E_INVALID, a kind no
+ * learner has is RL_E_UNSUPPORTED, each naming the learner.  The handle supplies nothing but its presence; it need not be bound. */
+int rl_learn_merge(rl_world* h, const rl_learner* learners, int n_learners, const float* rows, int n_ranks, int64_t row_stride_floats,
+                   void* stream);
+/* rl_policy_pack_weights on the device, all five kinds, ONE launch: params device [rl_policy_n_params(kind)] -> packed device
+ * [rl_policy_packed_floats(kind)], 16-byte aligned.  Every float the host packer writes gets the same bits. */
+int rl_policy_pack_device(int kind, const float* params, float* packed, void* stream);
+
 /* ---- frames ---------------------------------------------------------------------------------------------------- */
 /* What the painter of Helpers/render.py:51-239 draws, as integers: pixels per cell, the body square (offset, side, border width), the
  * two eye squares (side, y offset, x offsets) and the food square (offset, side) inside a cell -- computed by the host with the

@@ -20,7 +20,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
             limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None, seed=0, rng=None, per_agent_api=False,
             fused=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
             learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
-            learn_td_priority=None):
+            learn_td_priority=None, learn_ranks=None):
     """Extra keyword-only arguments: n_worlds / device / seed / rng / synthetic_agents / refill_below (Environment); per_agent_api=True makes the reference's literal
     per-agent get_action / learn calls; fused (default: True for rng="philox" without per_agent_api) runs the loop through
     Environment.run -- whole chunks of ticks per launch, ending where the Tracker closes an interval -- instead of three launches
@@ -37,8 +37,8 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     ONE rl_learn that makes `learn_steps` (default 5, DQN.py:143) minibatch updates per brain -- batch 32, gamma 0.98, smooth-L1, Adam, only once a ring holds more than 1000 transitions -- copies agent ->
     target (DQN.py:83) and rewrites the packed weights the worlds act with, all on the same stream with no host round trip; after the
     loop the trained parameters are copied into the brains' modules, so save=True writes them.  Brains of other kinds stay frozen (a
-    warning names them).  Needs rng="philox", the fused path, static_families=True, training=True and a single rank (ValueError
-    otherwise).  TWO DEVIATIONS from the reference: (1) the schedule -- the reference calls train() per agent whenever its age is a
+    warning names them).  Needs rng="philox", the fused path, static_families=True, training=True and a single rank -- or several with learn_ranks="average", below --
+    (ValueError otherwise).  TWO DEVIATIONS from the reference: (1) the schedule -- the reference calls train() per agent whenever its age is a
     multiple of train_freq or it died (DQN.py:85-89: over a thousand dependent train() calls per tick at 256 worlds); here a brain
     trains once per `learn_every` ticks of world time, as a single long-lived agent would cause; (2) minibatches are drawn uniformly
     WITH replacement, where the reference's random.sample (DQN.py:100) draws without -- and by a key of the rows' content mixed with
@@ -90,7 +90,19 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     update.  DEVIATIONS: the reference's sample() is stratified through its sum tree -- here the 64 draws are independent with
     probability p_i / sum p, by content key, with replacement; the schedule is per `learn_every` episodes, so brain.epsilon decays
     once per update made, not once per agent trigger (pass a smaller explore_step for the reference's rate in wall-clock terms).  Until a
-    ring first holds train_start rows each learning call reads its count back (a synchronisation); afterwards none does."""
+    ring first holds train_start rows each learning call reads its count back (a synchronisation); afterwards none does.
+    learn_ranks (default None: learning needs a single rank, as before; "average" needs learn="device", anything else is a ValueError
+    before a device is touched): training on several ranks, THIS BUILD'S OWN -- the reference has no multi-process training.  Every
+    rank trains its learners on its own rings exactly as above (draws, calls, priorities and PPO windows are rank-local and unchanged).
+    At set-up the ranks compare a signature of their learners and schedule (a mismatch raises on every rank), take rank 0's parameters
+    by one broadcast, zero Adam's moments and repack on the device.  Every learning episode then ends with one launch that exports the
+    learners into a row, ONE all-gather of the rows, and two launches that merge them (rl_learn_merge): per learner the ranks with the
+    highest Adam step count take part, params / adam_m / adam_v become their mean -- summed in rank order in double, rounded once, the
+    same bits on every rank -- the step count the maximum, the target the merged params where it was synced in this episode, and the
+    packed acting weights are rewritten from the merged params.  This is periodic PARAMETER averaging, not gradient averaging: D3QN,
+    PERD3QN and PERDQN make one update per episode from identical parameters and moments (the mean of R one-step Adam updates); DQN
+    makes learn_steps local steps and PPO k_epoch per rollout before the ranks meet.  Rings, priorities, windows, beta and a PERDQN's
+    host-side epsilon stay rank-local.  The merge also runs on one rank and without a process group (the identity, three launches)."""
     if learn == "device" and (per_agent_api or fused is False):
         raise ValueError("trainer(learn='device') needs the fused path (fused=True, per_agent_api=False): the replay rings are filled "
                          "inside the multi-tick launches")
@@ -101,7 +113,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
                       device=device, seed=seed, rng=rng, synthetic_agents=synthetic_agents, refill_below=refill_below, dist=dist,
                       world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps, learn_kinds=learn_kinds,
                       learn_prioritized=learn_prioritized, learn_rollout=learn_rollout, rollout_steps=rollout_steps,
-                      learn_td_priority=learn_td_priority)
+                      learn_td_priority=learn_td_priority, learn_ranks=learn_ranks)
     env.reset()
     if fused is None:
         fused = env.rng == "philox" and not per_agent_api

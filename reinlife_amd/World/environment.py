@@ -159,7 +159,7 @@ class Environment:
                  pastel_colors=False, limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None,
                  seed=0, rng=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
                  learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
-                 learn_td_priority=None):
+                 learn_td_priority=None, learn_ranks=None):
         if not brains:
             raise ValueError("Environment needs a non-empty list of brains")
         if learn not in (None, "device"):
@@ -205,6 +205,14 @@ class Environment:
         if learn_td_priority and not any(getattr(b, "method", None) == "PERDQN" for b in brains):
             raise ValueError("learn_td_priority=True needs at least one Models.PERDQN brain (got %s)" % ", ".join(str(getattr(b, "method", b)) for b in brains))
         self.learn_td_priority = bool(learn_td_priority)
+        # learn_ranks="average": the ranks of a process group train independently and merge their learners at the end of every learn_now
+        # (periodic parameter averaging; this build's own, the reference has no multi-process training).  Checked before a device is touched.
+        if learn_ranks not in (None, "average"):
+            raise ValueError("learn_ranks must be None (learning runs on a single rank) or 'average' (every rank trains on its own rings and the "
+                             "ranks average their learners after every learning episode), got %r" % (learn_ranks,))
+        if learn_ranks and learn != "device":
+            raise ValueError("learn_ranks='average' needs learn='device' (got learn=%r)" % (learn,))
+        self.learn_ranks = learn_ranks
         # learn_steps: minibatch updates per call -- an int is the DQN learners' (as always), a dict by method name sets it per kind;
         # D3QN defaults to 1 (D3QNAgent.train() makes one update), and so does PERDQN (train_model())
         self.learn_steps_of = {"DQN": 5, "D3QN": 1, "PERDQN": 1}
@@ -265,8 +273,11 @@ class Environment:
                 raise ValueError("learn='device' needs static_families=True: per-gene brain copies (non-static families) do not learn yet")
             if not training:
                 raise ValueError("learn='device' needs training=True")
-            if self.world_size > 1:
-                raise ValueError("learn='device' runs on a single rank: multi-rank training needs a weight collective (world size %d)" % self.world_size)
+            if self.world_size > 1 and not learn_ranks:
+                raise ValueError("learn='device' runs on a single rank: multi-rank training needs a weight collective (world size %d) -- "
+                                 "learn_ranks=\"average\" is it: the ranks then average their learners after every learning episode" % self.world_size)
+            if learn_ranks and self.world_size > _lib.MAX_MERGE_RANKS:
+                raise ValueError("learn_ranks='average' merges the learners of at most %d ranks (world size %d)" % (_lib.MAX_MERGE_RANKS, self.world_size))
             if len(brains) > _lib.MAX_CAPTURE_BRAINS:
                 raise ValueError("learn='device' captures transitions for at most %d brains (got %d)" % (_lib.MAX_CAPTURE_BRAINS, len(brains)))
             if min(self.learn_steps_of.values()) < 1 or (learn_every is not None and int(learn_every) < 1):
@@ -297,6 +308,8 @@ class Environment:
         self._ticks_since_check = 0
         self.loop_seconds = None    # wall time of the last trainer() / tester() loop on this environment (set by them)
         self.learn_every = None
+        self.learn_now_calls = 0    # learn_now() calls so far (learn_ranks="average": one collective each under a process group)
+        self._merge_row = None      # learn_ranks="average": the row this rank's learners are exported into
         if learn == "device":
             # the replay rings of DQN.py:15 (buffer_limit), filled inside the multi-tick launches; one learner per brain rl_learn trains,
             # whose packed tensor IS that brain's acting weights from here on (rl_learn rewrites it in place)
@@ -337,8 +350,52 @@ class Environment:
                 warn_inference_only(frozen, self.learn_kinds + (("PERD3QN (prioritised)",) if self.learn_prioritized else ())
                                     + (("PPO (rollouts)",) if self.learn_rollout else ())
                                     + (("PERDQN (TD priorities)",) if self.learn_td_priority else ()))
+            if self.learn_ranks:
+                self._align_learners()
         elif training:
             warn_inference_only()
+
+    def _align_learners(self):
+        """Set-up of learn_ranks="average": the ranks build their brains from their own torch generators, so they start from rank 0's
+        parameters -- one signature gather (the same learners, with the same exploration and soft_update_freq, on the same schedule everywhere,
+        or the same ValueError on every rank) and
+        ONE broadcast of all learners' params; then target = params (PPO has none), Adam's moments zero, and the acting weights repacked
+        on the device (rl_policy_pack_device).  Without a process group there is nothing to align: a fresh learner is in that state already."""
+        if self.dist is None:
+            return
+        from ..distributed import broadcast_from_rank0, check_learner_signature
+        ls = [self.learners[k] for k in sorted(self.learners)]
+        entries = ("rl_learn", "rl_learn_dueling", "rl_learn_prioritized", "rl_learn_ppo", "rl_learn_td")
+        sig = [len(ls)]
+        for k in sorted(self.learners):
+            l = self.learners[k]   # (exploration and soft_update_freq decide whether a learner is called and when its target is synced)
+            sig += [k, l.kind, entries.index(l.entry), getattr(l, "exploration", 0), getattr(l, "soft_update_freq", 0)]
+        sig += [self.learn_every, self.learn_steps_of["DQN"], self.learn_steps_of["D3QN"], self.learn_steps_of["PERDQN"], self.rollout_steps]
+        check_learner_signature(sig, self.dist, device=self.worlds.device)
+        flat = torch.cat([l.params for l in ls])
+        broadcast_from_rank0(flat, self.dist)
+        for l, part in zip(ls, flat.split([l.n_params for l in ls])):
+            l.params.copy_(part)
+            if l.target is not None:
+                l.target.copy_(l.params)
+            l.adam_m.zero_(); l.adam_v.zero_()
+            self.worlds.pack_device(l.kind, l.params, l.packed)
+
+    def _merge_learners(self, called):
+        """The end of a learning episode under learn_ranks="average": export -> ONE all-gather -> merge, for all learners at once
+        (DeviceWorlds.export_learners / merge_learners).  `called`: the learners this episode's calls were made for -- only their
+        sync_target flags count (a D3QN learner still below its exploration keeps its target).  Without a process group the merge runs
+        straight from the exported row (n_ranks = 1: the identity), so the path is the same in one process."""
+        ls = [self.learners[k] for k in sorted(self.learners)]
+        if self._merge_row is None:
+            self._merge_row = torch.empty(sum(l.merge_floats for l in ls), dtype=torch.float32, device=self.worlds.device)
+        row = self.worlds.export_learners(ls, out=self._merge_row)
+        rows, n_ranks = row, 1
+        if self.dist is not None:
+            from ..distributed import gather_learner_rows
+            rows = gather_learner_rows(row, self.dist).to(self.worlds.device)   # (under gloo the table arrives on the host)
+            n_ranks = self.world_size
+        self.worlds.merge_learners(ls, rows, n_ranks, sync_target=[bool(l.sync_target) and any(l is c for c in called) for l in ls])
 
     # -- the host view of the device state: materialised on first read after every state change ------------------------------
     @property
@@ -652,6 +709,10 @@ class Environment:
         if frozen:
             note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if (duel or prio or ppo or td) else
                         "brains %s as loaded / initialised (their kinds do not learn in this build)" % frozen)
+        if self.learn_ranks:
+            note.append("%d rank(s) trained independently on their own rings and averaged params, adam_m and adam_v over the ranks with the "
+                        "highest step count after every learning episode (learn_ranks='average': periodic parameter averaging, this build's own)"
+                        % self.world_size)
         return "; ".join(note)
 
     def learn_now(self, last=None):
@@ -672,10 +733,17 @@ class Environment:
         exploration gate; below brain.train_start rows the call only copies model -> target_model (PERDQNAgent.learn).  train_model()'s
         epsilon decay follows on the host: once per update made.  Whether a call trained depends on the ring's count, which lives on the
         device: it is read back once per call until it first reaches train_start (it never falls again) -- these early calls SYNCHRONISE
-        with the device; later ones do not."""
+        with the device; later ones do not.
+        learn_ranks="average": all of the above is rank-local and unchanged; the call then ends with the merge of ALL learners over the
+        ranks (_merge_learners: one launch to export, ONE all-gather, two launches to merge) -- this build's own, periodic parameter
+        averaging: D3QN, PERD3QN and PERDQN learners make one update per call from identical parameters and moments, so the merged
+        result is the mean of the ranks' one-step Adam updates; DQN makes learn_steps local steps and PPO k_epoch per rollout in between."""
+        self.learn_now_calls += 1
+        called = []
         dqn = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn"]
         if dqn:
             self.worlds.learn(dqn, self.learn_steps, slots=self.worlds.draw_slots(dqn, self.learn_steps))
+            called += dqn
         duel = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_dueling"
                 and (last is None or last > self.learners[k].exploration)]
         n = self.learn_steps_of["D3QN"]
@@ -685,6 +753,7 @@ class Environment:
                 for l in ls:
                     l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
             self.worlds.learn(ls, n, slots=self.worlds.draw_slots(ls, n))
+            called += ls
         prio = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_prioritized"
                 and (last is None or last > self.learners[k].exploration)]
         for batch in sorted({l.batch for l in prio}):
@@ -693,14 +762,17 @@ class Environment:
                 for l in ls:
                     l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
             self.worlds.learn(ls, 1, slots=self.worlds.draw_prioritized(ls, 1))
+            called += ls
         ppo = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_ppo"]
         if ppo:
             self.worlds.learn(ppo, self.rollout_steps, slots=self.worlds.draw_rollout(ppo, self.rollout_steps))
+            called += ppo
         td = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_td"]
         n = self.learn_steps_of["PERDQN"]
         for batch in sorted({l.batch for l in td}):
             ls = [l for l in td if l.batch == batch]
             self.worlds.learn(ls, n, slots=self.worlds.draw_td(ls, n))
+            called += ls
             for l in ls:
                 if not l.trained_from:   # (a read-back: only until the ring first holds train_start rows)
                     l.trained_from = min(int(l.ring["count"].item()), int(l.ring["state"].shape[0])) >= l.train_start
@@ -708,6 +780,8 @@ class Environment:
                     for _ in range(n):
                         if l.brain.epsilon > l.brain.epsilon_min:
                             l.brain.epsilon -= l.brain.epsilon_decay
+        if self.learn_ranks:
+            self._merge_learners(called)
 
     def sync_learners(self):
         """The trained parameters into the brains' modules (DeviceLearner.sync_to_module): what Saver and state_dict() read."""

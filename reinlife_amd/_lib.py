@@ -88,6 +88,7 @@ SITE_LEARN_PRIO = 11     # RL_SITE_LEARN_PRIO: the Philox site of rl_learn_prior
 SITE_LEARN_ROLLOUT = 12  # RL_SITE_LEARN_ROLLOUT: the Philox site of rl_learn_rollout's draws
 SITE_LEARN_TD = 13       # RL_SITE_LEARN_TD: the Philox site of rl_learn_td_draw's draws
 MAX_CAPTURE_BRAINS = 16  # RL_MAX_CAPTURE_BRAINS
+MAX_MERGE_RANKS = 64     # rl_learn_merge: n_ranks at most
 PPO_ROLLOUT_MAX = 32     # RL_PPO_ROLLOUT_MAX: the rows of a rollout at most (rl_learn_ppo)
 
 
@@ -140,6 +141,10 @@ ABI = [
     ("rl_learn_td_supported", C.c_int, [C.c_int]),
     ("rl_learn_td_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_td", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_merge_floats", C.c_int64, [C.c_int]),
+    ("rl_learn_export", C.c_int, [_P, C.POINTER(Learner), C.c_int, _P, _P]),
+    ("rl_learn_merge", C.c_int, [_P, C.POINTER(Learner), C.c_int, _P, C.c_int, C.c_int64, _P]),
+    ("rl_policy_pack_device", C.c_int, [C.c_int, _P, _P, _P]),
     ("rl_render", C.c_int, [_P, C.POINTER(RenderStyle), _P, C.c_int, _P, _P]),
     ("rl_set_option", C.c_int, [C.c_char_p, C.c_char_p]),
     ("rl_get_option", C.c_int, [_P, C.c_char_p]),

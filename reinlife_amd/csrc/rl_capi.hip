@@ -7,7 +7,7 @@
 
 #include "rl_common.h"
 
-// implemented in rl_world.hip / rl_policy.hip / rl_render.hip / rl_learn.hip / rl_learn_dueling.hip / rl_learn_prio.hip / rl_learn_td.hip
+// implemented in rl_world.hip / rl_policy.hip / rl_render.hip / rl_learn.hip / rl_learn_dueling.hip / rl_learn_prio.hip / rl_learn_td.hip / rl_learn_merge.hip
 size_t rl_world_smem_bytes(int cpad, int cap, int hash, int plane_stride, int height);
 int rl_world_block();
 int rl_world_launch_step(rl_world*, const int8_t*, const rl_tape*, const rl_step_out*, hipStream_t);
@@ -41,6 +41,10 @@ int rl_learn_td_draw_launch(rl_world*, const rl_learner*, const rl_replay*, cons
 int rl_learn_ppo_supported_impl(int);
 int rl_learn_ppo_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, const int32_t*, hipStream_t);
 int rl_learn_rollout_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, int32_t*, hipStream_t);
+int64_t rl_learn_merge_floats_impl(int);
+int rl_learn_export_launch(rl_world*, const rl_learner*, int, float*, hipStream_t);
+int rl_learn_merge_launch(rl_world*, const rl_learner*, int, const float*, int, int64_t, hipStream_t);
+int rl_policy_pack_device_launch(int, const float*, float*, hipStream_t);
 
 static thread_local char g_err[512] = "";
 
@@ -638,6 +642,59 @@ int rl_learn_td(rl_world* h, const rl_learner* learners, const rl_replay* rings,
     if (int rc = check_td("rl_learn_td", false, h, learners, rings, tds, n_learners, n_steps, slots)) return rc;
     DeviceGuard guard(device_of_pointer(learners[0].params));
     return rl_learn_td_launch(h, learners, rings, tds, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+int64_t rl_learn_merge_floats(int kind) { return rl_learn_merge_floats_impl(kind); }
+
+// what rl_learn_export and rl_learn_merge ask of their common arguments (`merge`: the merge also writes target and packed); *total: the
+// floats of the learners' segments laid end to end
+static int check_merge(const char* who, bool merge, rl_world* h, const rl_learner* learners, int n_learners, int64_t* total)
+{
+    if (!h) { rl_set_error("%s: null handle", who); return RL_E_INVALID; }
+    if (!learners) { rl_set_error("%s: null learners", who); return RL_E_INVALID; }
+    if (n_learners < 1 || n_learners > RL_MAX_CAPTURE_BRAINS) { rl_set_error("%s: n_learners must be in [1,%d] (got %d)", who, RL_MAX_CAPTURE_BRAINS, n_learners); return RL_E_INVALID; }
+    *total = 0;
+    for (int i = 0; i < n_learners; ++i) {
+        const rl_learner& l = learners[i];
+        const int64_t seg = rl_learn_merge_floats_impl(l.kind);
+        if (seg < 0) { rl_set_error("%s: learner %d has brain kind %d; no learner of this library has that kind (RL_DQN 0 .. RL_PERDQN 4)", who, i, l.kind); return RL_E_UNSUPPORTED; }
+        if (!l.params || !l.adam_m || !l.adam_v || !l.state) { rl_set_error("%s: learner %d: params / adam_m / adam_v / state must not be null", who, i); return RL_E_INVALID; }
+        if (merge && !l.packed) { rl_set_error("%s: learner %d: packed must not be null", who, i); return RL_E_INVALID; }
+        if (merge && !l.target && l.kind != RL_PPO) { rl_set_error("%s: learner %d: target must not be null (only an RL_PPO learner has none)", who, i); return RL_E_INVALID; }
+        *total += seg;
+    }
+    return RL_OK;
+}
+
+int rl_learn_export(rl_world* h, const rl_learner* learners, int n_learners, float* row, void* stream)
+{
+    int64_t total;
+    if (int rc = check_merge("rl_learn_export", false, h, learners, n_learners, &total)) return rc;
+    if (!row) { rl_set_error("rl_learn_export: null row (learners 0..%d need %lld floats)", n_learners - 1, (long long)total); return RL_E_INVALID; }
+    DeviceGuard guard(device_of_pointer(row));
+    return rl_learn_export_launch(h, learners, n_learners, row, (hipStream_t)stream);
+}
+
+int rl_learn_merge(rl_world* h, const rl_learner* learners, int n_learners, const float* rows, int n_ranks, int64_t row_stride_floats, void* stream)
+{
+    int64_t total;
+    if (int rc = check_merge("rl_learn_merge", true, h, learners, n_learners, &total)) return rc;
+    if (!rows) { rl_set_error("rl_learn_merge: null rows (learners 0..%d need %lld floats per rank)", n_learners - 1, (long long)total); return RL_E_INVALID; }
+    if (n_ranks < 1 || n_ranks > 64) { rl_set_error("rl_learn_merge: n_ranks must be in [1,64] (got %d; learners 0..%d)", n_ranks, n_learners - 1); return RL_E_INVALID; }
+    if (row_stride_floats < total) {
+        rl_set_error("rl_learn_merge: row_stride_floats %lld is shorter than the learners' segments: learner %d ends at float %lld", (long long)row_stride_floats, n_learners - 1, (long long)total);
+        return RL_E_INVALID;
+    }
+    DeviceGuard guard(device_of_pointer(learners[0].params));
+    return rl_learn_merge_launch(h, learners, n_learners, rows, n_ranks, row_stride_floats, (hipStream_t)stream);
+}
+
+int rl_policy_pack_device(int kind, const float* params, float* packed, void* stream)
+{
+    if (kind < RL_DQN || kind > RL_PERDQN) { rl_set_error("rl_policy_pack_device: unknown brain kind %d", kind); return RL_E_INVALID; }
+    if (!params || !packed) { rl_set_error("rl_policy_pack_device: kind %d: params / packed must not be null", kind); return RL_E_INVALID; }
+    DeviceGuard guard(device_of_pointer(packed));
+    return rl_policy_pack_device_launch(kind, params, packed, (hipStream_t)stream);
 }
 
 void rl_philox(uint64_t seed, uint32_t epoch, uint32_t world, uint32_t tick, uint32_t site, uint32_t index, uint32_t out[4])

@@ -87,6 +87,7 @@ class DeviceLearner:
         self.brain, self.kind, self.device = brain, brain.kind, torch.device(device)
         flat = brain.state_dict_flat()
         self.n_params = int(lib.rl_policy_n_params(self.kind))
+        self.merge_floats = int(lib.rl_learn_merge_floats(self.kind))   # this learner's segment of an exported row: params | adam_m | adam_v | step count
         self.params = torch.as_tensor(flat, device=self.device)
         self.target = None if rollout else self.params.clone()  # DQN.py:50 / D3QN.py:60 (PPO has no target network)
         self.adam_m = torch.zeros_like(self.params)
@@ -139,10 +140,12 @@ class DeviceLearner:
         self.loss = None          # optional device float32 [n_steps]
         self.grad = None          # optional device float32 [n_steps, n_params] (tests, diagnostics)
 
-    def struct(self):
+    def struct(self, sync_target=None):
+        """rl_learner.  sync_target: this call's flag instead of the learner's own (DeviceWorlds.merge_learners)."""
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         return _lib.Learner(self.kind, p(self.params), p(self.target), p(self.adam_m), p(self.adam_v), p(self.state), p(self.packed),
-                            self.lr, self.gamma, self.beta1, self.beta2, self.eps, self.batch, self.min_size, int(self.sync_target),
+                            self.lr, self.gamma, self.beta1, self.beta2, self.eps, self.batch, self.min_size,
+                            int(self.sync_target if sync_target is None else sync_target),
                             p(self.loss), p(self.grad))
 
     def ring_struct(self):

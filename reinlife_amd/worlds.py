@@ -554,6 +554,57 @@ class DeviceWorlds:
         self._learn_keep = slots   # (the launch reads the table asynchronously)
         self.launches += 1
 
+    def export_learners(self, learners, out=None):
+        """The learners' state as ONE flat float32 row on the device (rl_learn_export, one launch, queued on the current stream): learner i's
+        segment -- params | adam_m | adam_v | its Adam step count as two 32-bit words -- starts where learner i - 1's ends
+        (DeviceLearner.merge_floats each).  What the ranks of a job all-gather before merge_learners().  out: a row to fill."""
+        n = len(learners)
+        if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
+            raise ValueError("export_learners(): 1 to %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
+        total = sum(l.merge_floats for l in learners)
+        if out is None:
+            out = torch.empty(total, dtype=torch.float32, device=self.device)
+        elif out.numel() < total or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("export_learners(): out must be a contiguous float32 device tensor of at least %d elements" % total)
+        arr = (_lib.Learner * n)(*[l.struct() for l in learners])
+        _lib.check(self.lib.rl_learn_export(self.handle, arr, n, _ptr(out), self._stream()), "rl_learn_export")
+        self.launches += 1
+        return out
+
+    def merge_learners(self, learners, rows, n_ranks, sync_target=None):
+        """The end of a learning episode on several ranks (rl_learn_merge, two launches, queued on the current stream): `rows` is the
+        all-gather of the ranks' exported rows, a float32 device tensor [n_ranks, floats] (a flat row when n_ranks == 1).  Per learner the
+        ranks with the highest Adam step count take part; params, adam_m and adam_v become their mean (summed in rank order in double,
+        rounded once: the same bits on every rank), the step count the maximum, target the merged params where the learner's sync_target
+        is set (sync_target: a list of flags for THIS call instead), and packed is rewritten from the merged params like the host packer
+        does.  This build's own: periodic parameter averaging, not gradient averaging; the reference has no multi-process training."""
+        n = len(learners)
+        if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
+            raise ValueError("merge_learners(): 1 to %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
+        n_ranks = int(n_ranks)
+        if n_ranks < 1 or n_ranks > _lib.MAX_MERGE_RANKS:
+            raise ValueError("merge_learners(): 1 to %d ranks (got %d)" % (_lib.MAX_MERGE_RANKS, n_ranks))
+        if not (torch.is_tensor(rows) and rows.is_cuda and rows.dtype == torch.float32 and rows.is_contiguous()):
+            raise ValueError("merge_learners(): rows must be a contiguous float32 device tensor")
+        if rows.numel() % n_ranks:
+            raise ValueError("merge_learners(): rows holds %d floats, no multiple of n_ranks %d" % (rows.numel(), n_ranks))
+        flags = [None] * n if sync_target is None else list(sync_target)
+        arr = (_lib.Learner * n)(*[l.struct(sync_target=f) for l, f in zip(learners, flags)])
+        _lib.check(self.lib.rl_learn_merge(self.handle, arr, n, _ptr(rows), n_ranks, rows.numel() // n_ranks, self._stream()), "rl_learn_merge")
+        self._merge_keep = rows   # (the launches read the table asynchronously)
+        self.launches += 2
+
+    def pack_device(self, kind, params, packed):
+        """rl_policy_pack_weights on the device (rl_policy_pack_device, one launch on the current stream): `params` (device float32, state-dict
+        order) -> `packed` (device float32 [rl_policy_packed_floats(kind)]), the host packer's bits."""
+        if params.numel() != self.lib.rl_policy_n_params(kind) or packed.numel() != self.lib.rl_policy_packed_floats(kind):
+            raise ValueError("pack_device(): brain kind %d takes %d parameters and %d packed floats (got %d, %d)"
+                             % (kind, self.lib.rl_policy_n_params(kind), self.lib.rl_policy_packed_floats(kind), params.numel(), packed.numel()))
+        if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (params, packed)):
+            raise ValueError("pack_device(): params and packed must be contiguous float32 device tensors")
+        _lib.check(self.lib.rl_policy_pack_device(int(kind), _ptr(params), _ptr(packed), self._stream()), "rl_policy_pack_device")
+        self.launches += 1
+
     def reset_tracking(self):
         if self._trk_dirty:   # (fresh accumulators are zero: a new Environment's first launch is not preceded by three memsets)
             self.trk_sum.zero_(); self.trk_cnt.zero_(); self.trk_pop[:, 1:].zero_()
