@@ -16,6 +16,7 @@
  *   rl_render          Visualize.render()'s drawing of one frame, for any set of worlds     Helpers/render.py:51-239
  *   rl_learn           DQNAgent.train(): the size gate, 5 minibatch updates (smooth-L1, Adam) and the target copy
  *                      Models/DQN.py:80-83, 142-153 (sampling: :99-113, with replacement here)
+ *   rl_learn_wide      the same update on minibatches of up to 2048 rows, 32-row tiles side by side (DQN.py:80-83, 142-153)
  *   rl_learn_ppo       PPO.learn(): k_epoch full-batch Adam steps on a rollout of at most 32 rows (rl_learn_rollout draws it)
  *   rl_learn_dueling   D3QNAgent.train(): one minibatch update of the dueling network (MSE, Adam), batch up to 64
  *                      Models/D3QN.py:97-116, 148-165 (schedule and target copy of :118-126: the caller's)
@@ -383,6 +384,44 @@ int rl_learn_dueling(rl_world* h, const rl_learner* learners, const rl_replay* r
  * differs from run to run. */
 int rl_learn_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps,
                   unsigned long long* const* keys, int32_t* slots, void* stream);
+
+/* ---- wide minibatches (DQN) -------------------------------------------------------------------------------------- */
+/* THIS BUILD'S OWN -- the reference trains one world on minibatches of 32 (DQN.py:80-83, 142-153).  rl_learn_wide is that update on a
+ * minibatch of 1 .. RL_LEARN_WIDE_MAX rows, split into 32-row tiles that run side by side, one workgroup per (learner, tile): a run of
+ * many worlds appends far more rows per learning episode than 5 x 32, and rl_learn keeps one CU busy.  A call whose batch is at most 32
+ * (one tile) leaves every buffer bit for bit as rl_learn leaves it.  rl_learn, rl_learn_draw and rl_learn_supported are unchanged by it. */
+#define RL_LEARN_WIDE_MAX 2048
+/* 1 for the brain kinds rl_learn_wide trains (RL_DQN), 0 for the others */
+int rl_learn_wide_supported(int kind);
+/* The bytes of one learner's work buffer for a minibatch of `batch` rows: a 64-byte header, ceil(batch / 32) rows of
+ * rl_policy_n_params(kind) floats (the tiles' partial gradients), and the tiles' loss sums, rounded up to 16 bytes.  0, with
+ * rl_last_error set, for a kind rl_learn_wide does not train or a batch outside [1, RL_LEARN_WIDE_MAX]. */
+size_t rl_learn_wide_work_bytes(int kind, int batch);
+/* DQNAgent.train() (DQN.py:80-83 -> train(), :142-153) on wide minibatches for n_learners brains, on the rl_learner / rl_replay
+ * structures of rl_learn (kind must be RL_DQN; batch in [1, RL_LEARN_WIDE_MAX], ONE batch for all learners of a call).
+ *   work        host array [n_learners] of device buffers of at least rl_learn_wide_work_bytes(kind, batch) bytes each, 16-byte aligned;
+ *               they need no initialisation and hold nothing between calls
+ *   size gate   as rl_learn: size = min(*ring.count, ring.capacity), read on the device; size <= min_size: no update
+ *   rows        slots != NULL: device int32 [n_learners][n_steps][batch]; every entry of a learner that trains is range-checked
+ *               before a row is fetched -- a bad one sets error-flag code 6 ([1] = learner, [2] = step, [3] = the value; the first in
+ *               table order) and that learner leaves the call with NONE of its buffers touched (the others train).  slots == NULL:
+ *               rl_learn's draw with the wider batch: slot = ((uint64)x * size) >> 32, x = word 0 of rl_philox(seed, 0, i,
+ *               (uint32)state[1], RL_SITE_LEARN, s * batch + j).  Tile t of a step holds batch rows 32 t .. min(32 t + 31, batch - 1).
+ *   a step      every tile runs rl_learn's forward, smooth-L1 and backward arithmetic on its rows, with the loss gradient scaled by
+ *               1.0f / batch of the WHOLE batch, and writes its partial gradient (per parameter the f32 sum over the tile's rows,
+ *               ascending: what rl_learn hands to Adam) and its loss sum to `work`.  Then one thread per parameter adds the tiles'
+ *               partials in tile order in double, rounds to float once -- with one tile: the partial itself -- and makes rl_learn's Adam
+ *               update with it.  loss[s] = (float)(sum of the tiles' loss sums in double) * (1.0f / batch); grad[s] = the summed gradient.
+ *   afterwards  as rl_learn: sync_target != 0: target <- params (also below the size gate); state[0] += updates made; state[1] += 1;
+ *               `packed` rewritten from the final params, bit for bit what rl_policy_pack_weights(RL_DQN, ...) makes of them.
+ * 2 n_steps + 3 launches, all queued on `stream`: one check pass (gate, slots, header), per step the tiles and the update, one pass for
+ * target and counters, one for `packed`.  No host read-back, no cooperative launch, no allocation.  Deterministic: every sum has a fixed
+ * order and no float atomics exist, so the same buffers give the same bits in every run and whatever else is in the launch.
+ * Validated on the host before anything is launched, RL_E_INVALID naming the argument (here also for a kind that is not RL_DQN):
+ * null handle / learners / rings / work, n_learners in [1, RL_MAX_CAPTURE_BRAINS], n_steps >= 1, batch in [1, RL_LEARN_WIDE_MAX] and
+ * equal for all learners, rl_learn's null-pointer and capacity checks, a null work[i]. */
+int rl_learn_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, const int32_t* slots,
+                  void* const* work, void* stream);
 
 /* ---- prioritised replay (PERD3QN) ------------------------------------------------------------------------------- */
 /* The prioritised memory of one learning PERD3QN brain (PrioritizedReplayBuffer, Models/PERD3QN.py:133-182) beside its rl_replay ring:

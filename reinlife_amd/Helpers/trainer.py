@@ -20,7 +20,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
             limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None, seed=0, rng=None, per_agent_api=False,
             fused=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
             learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
-            learn_td_priority=None, learn_ranks=None):
+            learn_td_priority=None, learn_ranks=None, learn_batch=None):
     """Extra keyword-only arguments: n_worlds / device / seed / rng / synthetic_agents / refill_below (Environment); per_agent_api=True makes the reference's literal
     per-agent get_action / learn calls; fused (default: True for rng="philox" without per_agent_api) runs the loop through
     Environment.run -- whole chunks of ticks per launch, ending where the Tracker closes an interval -- instead of three launches
@@ -102,7 +102,14 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     packed acting weights are rewritten from the merged params.  This is periodic PARAMETER averaging, not gradient averaging: D3QN,
     PERD3QN and PERDQN make one update per episode from identical parameters and moments (the mean of R one-step Adam updates); DQN
     makes learn_steps local steps and PPO k_epoch per rollout before the ranks meet.  Rings, priorities, windows, beta and a PERDQN's
-    host-side epsilon stay rank-local.  The merge also runs on one rank and without a process group (the identity, three launches)."""
+    host-side epsilon stay rank-local.  The merge also runs on one rank and without a process group (the identity, three launches).
+    learn_batch (default None: every run is bit for bit what it was; an int in [1, 2048] needs learn="device" and at least one Models.DQN
+    among the learning kinds, ValueError otherwise, before a device is touched): THIS BUILD'S OWN -- the reference's minibatch is 32 rows
+    (DQN.py:16), sized for one world.  Every DQN learner then trains through rl_learn_wide: each of the `learn_steps` updates is one Adam
+    step on a minibatch of learn_batch rows, computed in 32-row tiles that run side by side (one workgroup per brain and tile) and
+    summed in tile order in double -- the same bits in every run.  Draw, schedule, gate (1000 rows), gamma, loss and target copy are the
+    DQN learners'; a call is 2 learn_steps + 3 launches instead of one.  learn_batch=32 gives the parameters learn_batch=None gives, bit
+    for bit.  The learning rate stays the brain's: a wider batch averages more rows per step, it does not take more steps."""
     if learn == "device" and (per_agent_api or fused is False):
         raise ValueError("trainer(learn='device') needs the fused path (fused=True, per_agent_api=False): the replay rings are filled "
                          "inside the multi-tick launches")
@@ -113,7 +120,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
                       device=device, seed=seed, rng=rng, synthetic_agents=synthetic_agents, refill_below=refill_below, dist=dist,
                       world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps, learn_kinds=learn_kinds,
                       learn_prioritized=learn_prioritized, learn_rollout=learn_rollout, rollout_steps=rollout_steps,
-                      learn_td_priority=learn_td_priority, learn_ranks=learn_ranks)
+                      learn_td_priority=learn_td_priority, learn_ranks=learn_ranks, learn_batch=learn_batch)
     env.reset()
     if fused is None:
         fused = env.rng == "philox" and not per_agent_api

@@ -159,7 +159,7 @@ class Environment:
                  pastel_colors=False, limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None,
                  seed=0, rng=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
                  learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
-                 learn_td_priority=None, learn_ranks=None):
+                 learn_td_priority=None, learn_ranks=None, learn_batch=None):
         if not brains:
             raise ValueError("Environment needs a non-empty list of brains")
         if learn not in (None, "device"):
@@ -205,6 +205,18 @@ class Environment:
         if learn_td_priority and not any(getattr(b, "method", None) == "PERDQN" for b in brains):
             raise ValueError("learn_td_priority=True needs at least one Models.PERDQN brain (got %s)" % ", ".join(str(getattr(b, "method", b)) for b in brains))
         self.learn_td_priority = bool(learn_td_priority)
+        # learn_batch=B: every DQN learner trains through rl_learn_wide on minibatches of B rows (1 .. 2048) in 32-row tiles side by side
+        # (this build's own: the reference's minibatch is 32, DQN.py:16).  None: rl_learn, as always.  Checked before a device is touched.
+        if learn_batch is not None:
+            if isinstance(learn_batch, bool) or not isinstance(learn_batch, (int, np.integer)) or not 1 <= learn_batch <= _lib.LEARN_WIDE_MAX:
+                raise ValueError("learn_batch must be None or an int in [1, %d] (the rows of a DQN minibatch, rl_learn_wide), got %r"
+                                 % (_lib.LEARN_WIDE_MAX, learn_batch))
+            if learn != "device":
+                raise ValueError("learn_batch needs learn='device' (got learn=%r)" % (learn,))
+            if "DQN" not in self.learn_kinds or not any(getattr(b, "method", None) == "DQN" for b in brains):
+                raise ValueError("learn_batch needs at least one Models.DQN brain among the learning kinds %r (got %s)"
+                                 % (self.learn_kinds, ", ".join(str(getattr(b, "method", b)) for b in brains)))
+        self.learn_batch = None if learn_batch is None else int(learn_batch)
         # learn_ranks="average": the ranks of a process group train independently and merge their learners at the end of every learn_now
         # (periodic parameter averaging; this build's own, the reference has no multi-process training).  Checked before a device is touched.
         if learn_ranks not in (None, "average"):
@@ -328,7 +340,8 @@ class Environment:
             else:
                 self.worlds.enable_capture(BUFFER_LIMIT, **prob)
             for k in entries:
-                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k])
+                wide = {"wide_batch": self.learn_batch} if self.learn_batch is not None and entries[k] == "rl_learn" else {}
+                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], **wide)
             for k in prio:
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], prioritized=True)
             for k in ppo:
@@ -365,11 +378,13 @@ class Environment:
             return
         from ..distributed import broadcast_from_rank0, check_learner_signature
         ls = [self.learners[k] for k in sorted(self.learners)]
-        entries = ("rl_learn", "rl_learn_dueling", "rl_learn_prioritized", "rl_learn_ppo", "rl_learn_td")
+        entries = ("rl_learn", "rl_learn_dueling", "rl_learn_prioritized", "rl_learn_ppo", "rl_learn_td", "rl_learn_wide")
         sig = [len(ls)]
         for k in sorted(self.learners):
             l = self.learners[k]   # (exploration and soft_update_freq decide whether a learner is called and when its target is synced)
             sig += [k, l.kind, entries.index(l.entry), getattr(l, "exploration", 0), getattr(l, "soft_update_freq", 0)]
+            if l.entry == "rl_learn_wide":   # (the other entry points' batches come from the brains' classes: the signatures of runs without learn_batch stay what they were)
+                sig += [l.batch]
         sig += [self.learn_every, self.learn_steps_of["DQN"], self.learn_steps_of["D3QN"], self.learn_steps_of["PERDQN"], self.rollout_steps]
         check_learner_signature(sig, self.dist, device=self.worlds.device)
         flat = torch.cat([l.params for l in ls])
@@ -666,6 +681,8 @@ class Environment:
                     "Max agents": self.max_agents, "Families": self.static_families,
                     # (extra key, not in the reference's file) which weights were updated: say so next to them
                     "Weights": self._weights_note()}
+        if self.learn_batch is not None:   # (extra key, only where the keyword was given)
+            settings["Learn batch"] = self.learn_batch
         if self.static_families:
             agents = [SavedAgent(g, b) for g, b in enumerate(self.brains)]
         else:  # the brains the best agents descend from (inference-time copies share their weights)
@@ -680,7 +697,11 @@ class Environment:
         dqn = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn")
         duel = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_dueling")
         prio = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_prioritized")
+        wide = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_wide")
         note = []
+        if wide:
+            note.append("brains %s trained on the device (rl_learn_wide: %d minibatch updates of batch %d (learn_batch) every %d episodes, rows drawn by "
+                        "content key with replacement)" % (wide, self.learn_steps, self.learn_batch, self.learn_every))
         if dqn:
             note.append("brains %s trained on the device (rl_learn: %d minibatch updates every %d episodes, rows drawn by content key with replacement)"
                         % (dqn, self.learn_steps, self.learn_every))
@@ -734,13 +755,16 @@ class Environment:
         epsilon decay follows on the host: once per update made.  Whether a call trained depends on the ring's count, which lives on the
         device: it is read back once per call until it first reaches train_start (it never falls again) -- these early calls SYNCHRONISE
         with the device; later ones do not.
+        learn_batch=B: the DQN learners are wide ones (rl_learn_wide, minibatches of B rows in 32-row tiles side by side) and are called in
+        the DQN learners' place, the same way: draw (draw_slots: the same flat table, so B = 32 trains on rl_learn's rows), then learn,
+        learn_steps steps -- 2 learn_steps + 3 launches instead of one.
         learn_ranks="average": all of the above is rank-local and unchanged; the call then ends with the merge of ALL learners over the
         ranks (_merge_learners: one launch to export, ONE all-gather, two launches to merge) -- this build's own, periodic parameter
         averaging: D3QN, PERD3QN and PERDQN learners make one update per call from identical parameters and moments, so the merged
         result is the mean of the ranks' one-step Adam updates; DQN makes learn_steps local steps and PPO k_epoch per rollout in between."""
         self.learn_now_calls += 1
         called = []
-        dqn = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn"]
+        dqn = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry in ("rl_learn", "rl_learn_wide")]   # (learn_batch: all wide)
         if dqn:
             self.worlds.learn(dqn, self.learn_steps, slots=self.worlds.draw_slots(dqn, self.learn_steps))
             called += dqn

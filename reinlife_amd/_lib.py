@@ -89,6 +89,7 @@ SITE_LEARN_ROLLOUT = 12  # RL_SITE_LEARN_ROLLOUT: the Philox site of rl_learn_ro
 SITE_LEARN_TD = 13       # RL_SITE_LEARN_TD: the Philox site of rl_learn_td_draw's draws
 MAX_CAPTURE_BRAINS = 16  # RL_MAX_CAPTURE_BRAINS
 MAX_MERGE_RANKS = 64     # rl_learn_merge: n_ranks at most
+LEARN_WIDE_MAX = 2048    # RL_LEARN_WIDE_MAX: the rows of a minibatch at most (rl_learn_wide)
 PPO_ROLLOUT_MAX = 32     # RL_PPO_ROLLOUT_MAX: the rows of a rollout at most (rl_learn_ppo)
 
 
@@ -129,6 +130,9 @@ ABI = [
     ("rl_policy_act", C.c_int, [_P, C.POINTER(Brain), C.c_int, _P, _P, _P, _P, _P]),
     ("rl_learn_supported", C.c_int, [C.c_int]),
     ("rl_learn", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_wide_supported", C.c_int, [C.c_int]),
+    ("rl_learn_wide_work_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("rl_learn_wide", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, _P, C.POINTER(_P), _P]),
     ("rl_learn_dueling_supported", C.c_int, [C.c_int]),
     ("rl_learn_dueling", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, C.POINTER(_P), _P, _P]),

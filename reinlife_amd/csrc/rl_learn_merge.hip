@@ -1,6 +1,7 @@
 // rl_learn_merge.hip -- what several ranks need to train together (include/reinlife_hip.h, "learning on several ranks"): a learner's
 // state as one flat row (k_merge_export), the deterministic mean of the rows of all ranks back into the learner (k_merge_mean), and
-// rl_policy.hip's host packer on the device for every brain kind (k_pack_device), which also serves rl_policy_pack_device.
+// rl_policy.hip's host packer on the device for every brain kind (k_pack_device), which also serves rl_policy_pack_device and the end
+// of an rl_learn_wide call.
 // This build's own: the reference has no multi-process training.  No matrix work, no LDS tiles: three memory-bound kernels.
 //
 // Row segment of one learner (rl_learn_merge_floats = 3 n_params + 2 floats): params | adam_m | adam_v | state[0] as two 32-bit words,
@@ -50,6 +51,7 @@ struct PackBrain {
     const float* params;
     float* packed;
     int kind;
+    const long long* bad;          // null, or one device word: non-zero leaves `packed` as it is (rl_learn_wide's learner with a bad slot)
 };
 struct PackArgs {
     PackBrain b[RL_MAX_CAPTURE_BRAINS];
@@ -190,6 +192,7 @@ __global__ __launch_bounds__(kMBlock) void k_pack_device(const PackArgs A)
 {
     __shared__ float sc[32], un[32];
     const PackBrain& B = A.b[blockIdx.y];
+    if (B.bad && *B.bad) return;   // (the whole workgroup)
     PackLayer ly[kMaxLayers];
     const int n_layers = pack_layers_of(B.kind, ly);
     int tile = blockIdx.x;
@@ -260,13 +263,21 @@ int rl_learn_merge_launch(rl_world*, const rl_learner* learners, int n_learners,
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { rl_set_error("rl_learn_merge: launch of the mean kernel failed: %s", hipGetErrorString(e)); return RL_E_LAUNCH; }
     PackArgs p{};
-    for (int i = 0; i < n_learners; ++i) p.b[i] = PackBrain{learners[i].params, learners[i].packed, learners[i].kind};
+    for (int i = 0; i < n_learners; ++i) p.b[i] = PackBrain{learners[i].params, learners[i].packed, learners[i].kind, nullptr};
     return launch_pack("rl_learn_merge", p, n_learners, stream);
+}
+
+// the packer at the end of an rl_learn_wide call: bad[i] is learner i's "bad slot" word, written earlier on the same stream
+int rl_learn_wide_pack_launch(const rl_learner* learners, int n_learners, const long long* const* bad, hipStream_t stream)
+{
+    PackArgs p{};
+    for (int i = 0; i < n_learners; ++i) p.b[i] = PackBrain{learners[i].params, learners[i].packed, learners[i].kind, bad[i]};
+    return launch_pack("rl_learn_wide", p, n_learners, stream);
 }
 
 int rl_policy_pack_device_launch(int kind, const float* params, float* packed, hipStream_t stream)
 {
     PackArgs p{};
-    p.b[0] = PackBrain{params, packed, kind};
+    p.b[0] = PackBrain{params, packed, kind, nullptr};
     return launch_pack("rl_policy_pack_device", p, 1, stream);
 }

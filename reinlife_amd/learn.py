@@ -1,4 +1,4 @@
-"""DeviceLearner: what a DQN, D3QN, (prioritized=True) PERD3QN, (rollout=True) PPO or (td_priority=True) PERDQN brain needs to learn on
+"""DeviceLearner: what a DQN (also on wide minibatches: wide_batch=, rl_learn_wide), D3QN, (prioritized=True) PERD3QN, (rollout=True) PPO or (td_priority=True) PERDQN brain needs to learn on
 the device (rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo / rl_learn_td, include/reinlife_hip.h) -- the flat f32 master parameters,
 the target network, Adam's moments, the step / call counters and the packed weights the acting kernels read, all as device tensors.
 
@@ -62,9 +62,16 @@ def entry_of(kind):
 
 
 class DeviceLearner:
-    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False, td_priority=False):
+    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False, td_priority=False, wide_batch=None):
         lib = _lib.lib()
-        if td_priority:   # an explicit opt-in, like prioritized and rollout: entry_of() and ENTRY_BY_METHOD keep answering what they answered
+        if wide_batch is not None:   # an explicit opt-in, like the three below: entry_of() and ENTRY_BY_METHOD keep answering what they answered
+            other = " with prioritized=True" if prioritized else " with rollout=True" if rollout else " with td_priority=True" if td_priority else ""
+            if other or not lib.rl_learn_wide_supported(brain.kind):
+                raise ValueError("wide_batch is for DQN brains (rl_learn_wide); got a %s brain (kind %d)%s" % (brain.method, brain.kind, other))
+            if isinstance(wide_batch, bool) or not isinstance(wide_batch, (int, np.integer)) or not 1 <= wide_batch <= _lib.LEARN_WIDE_MAX:
+                raise ValueError("wide_batch must be an int in [1, %d] (the rows of a minibatch of rl_learn_wide), got %r" % (_lib.LEARN_WIDE_MAX, wide_batch))
+            self.entry = "rl_learn_wide"
+        elif td_priority:   # an explicit opt-in, like prioritized and rollout: entry_of() and ENTRY_BY_METHOD keep answering what they answered
             if prioritized or rollout or not lib.rl_learn_td_supported(brain.kind):
                 raise ValueError("td_priority=True is for PERDQN brains (rl_learn_td); got a %s brain (kind %d)%s"
                                  % (brain.method, brain.kind, " with prioritized=True" if prioritized else " with rollout=True" if rollout else ""))
@@ -108,9 +115,9 @@ class DeviceLearner:
             self.min_size = self.train_start - 1                 # learn(): n_entries >= train_start
             self.n_steps_default = 1                             # train_model() makes one update
             self.sync_target = True                              # learn(): update_target_model() after every trigger
-        elif self.entry == "rl_learn":
+        elif self.entry in ("rl_learn", "rl_learn_wide"):   # the wide learner is the DQN learner with its own batch
             self.lr = float(getattr(brain, "learning_rate", 0.0005))
-            self.gamma, self.batch, self.min_size = GAMMA, BATCH, MIN_SIZE
+            self.gamma, self.batch, self.min_size = GAMMA, BATCH if wide_batch is None else int(wide_batch), MIN_SIZE
             self.n_steps_default = 5                             # DQN.py:143
             self.sync_target = True                              # DQN.py:83
         else:   # D3QN.py:54-72: the brain's own hyperparameters
@@ -137,6 +144,9 @@ class DeviceLearner:
         self.trained_from = False  # td_priority=True: the ring has reached train_start (Environment.learn_now reads it back until then)
         if td_priority and ring is not None:
             self._make_td()
+        self.work = None          # wide_batch: rl_learn_wide's scratch (header, the tiles' partial gradients and loss sums); needs no initialisation
+        if self.entry == "rl_learn_wide":
+            self.work = torch.empty(int(lib.rl_learn_wide_work_bytes(self.kind, self.batch)), dtype=torch.uint8, device=self.device)
         self.loss = None          # optional device float32 [n_steps]
         self.grad = None          # optional device float32 [n_steps, n_params] (tests, diagnostics)
 

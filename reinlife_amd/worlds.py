@@ -422,13 +422,13 @@ class DeviceWorlds:
         multi-tick launch appends the worlds' transitions in the order their workgroups reach an atomic counter, so two identical
         runs hold the same transitions in other slots; these draws pick rows by a key of their content -- uniform, with replacement,
         the same rows in every run.  Device int32 [len(learners), n_steps, batch], queued on the current stream.
-        rl_learn_draw's table is flat (draw d = s * batch + j) and its batch is at most 32, so for a larger batch (D3QN: 64) the same
+        rl_learn_draw's table is flat (draw d = s * batch + j) and its batch is at most 32, so for a larger batch (D3QN: 64, wide DQN: up to 2048) the same
         table is asked for as [n_steps * batch / b][b], b the largest divisor of batch that is <= 32 ([n_steps][64] = [2 n_steps][32])."""
         n = len(learners)
         if len({l.batch for l in learners}) != 1:
             raise ValueError("draw_slots(): the learners of a call must share one batch size")
         batch = int(learners[0].batch)
-        # any batch in [1, 64] works: a prime one such as 37 draws as [37 n_steps][1] -- more steps of one draw, the same flat table
+        # any batch works (rl_learn_wide: up to 2048): a prime one such as 37 draws as [37 n_steps][1] -- more steps of one draw, the same flat table
         draw_batch = max(b for b in range(1, min(batch, 32) + 1) if batch % b == 0)
         draw_steps = int(n_steps) * (batch // draw_batch)
         for l in learners:
@@ -521,7 +521,8 @@ class DeviceWorlds:
         PPO learners to rl_learn_ppo (PPO.learn(), PPO.py:136-162: n_steps rollouts of `batch` rows, k_epoch Adam steps each; `slots` from
         draw_rollout(), or the caller's own rows with gate=False, which leaves the empty-window gate out), a list of PERDQN learners to
         rl_learn_td (PERDQNAgent.train_model(): the loss scaled by the mean importance weight, the batch rows' priorities rewritten;
-        `slots` from draw_td()).  The
+        `slots` from draw_td()), a list of wide DQN learners (DeviceLearner(..., wide_batch=B)) to rl_learn_wide (the DQN update on
+        minibatches of B <= 2048 rows, 32-row tiles side by side, 2 n_steps + 3 launches; `slots` from draw_slots() or None).  The
         learners of one call must all belong to one entry point: ValueError otherwise."""
         if not learners:
             return
@@ -549,6 +550,10 @@ class DeviceWorlds:
         elif entry == "rl_learn_ppo":
             ppos = (_lib.Ppo * n)(*[l.ppo_struct(gate=gate) for l in learners])
             _lib.check(self.lib.rl_learn_ppo(self.handle, arr, rings, ppos, n, int(n_steps), _ptr(slots), self._stream()), entry)
+        elif entry == "rl_learn_wide":
+            work = (C.c_void_p * n)(*[l.work.data_ptr() for l in learners])
+            _lib.check(self.lib.rl_learn_wide(self.handle, arr, rings, n, int(n_steps), _ptr(slots), work, self._stream()), entry)
+            self.launches += 2 * int(n_steps) + 2   # (2 n_steps + 3 in all: check, tiles and update per step, target / counters, pack)
         else:
             _lib.check(getattr(self.lib, entry)(self.handle, arr, rings, n, int(n_steps), _ptr(slots), self._stream()), entry)
         self._learn_keep = slots   # (the launch reads the table asynchronously)
