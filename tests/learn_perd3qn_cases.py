@@ -164,15 +164,16 @@ def host_uniform_draw(keys, seed, brain, calls, n_draws, site=None):
     return np.array([int(np.argmin(_mix64(keys ^ s))) for s in salts], np.int64)   # (argmin: the first of equal values)
 
 
-def host_draw64(keys, weight32, seed, brain, calls, n_draws):
+def host_draw64(keys, weight32, seed, brain, calls, n_draws, site=None):
     """host_draw's integer part with t = -log(U) / weight in float64, from the float32 weights the device itself made (learner.weight
     read back), so that powf's rounding stays out of the comparison -> (the winner of every draw by (t, v, slot), the relative gap
-    (t_second - t_first) / t_first of every draw: +inf where no second row has a weight)."""
+    (t_second - t_first) / t_first of every draw: +inf where no second row has a weight).  site: another Philox site than
+    RL_SITE_LEARN_PRIO -- RL_SITE_LEARN_TD for rl_learn_td_draw, whose race weight is the stored priority itself."""
     from reinlife_amd import _lib
     keys, w = np.asarray(keys, np.uint64), np.asarray(weight32).astype(np.float64)
     slot = np.arange(len(keys))
     rows, gaps = np.zeros(n_draws, np.int64), np.zeros(n_draws)
-    for d, s in enumerate(_salts(seed, brain, calls, _lib.SITE_LEARN_PRIO, n_draws)):
+    for d, s in enumerate(_salts(seed, brain, calls, _lib.SITE_LEARN_PRIO if site is None else site, n_draws)):
         v = _mix64(keys ^ s)
         u = ((v >> np.uint64(41)).astype(np.float64) + 0.5) / 8388608.0
         t = np.full(len(keys), np.inf)

@@ -129,3 +129,28 @@ def stamp(priority, seen, count, p_new):
         for c in range(seen, count):
             out[c % cap] = p_new
     return out
+
+
+# ---- inputs beyond the fixture (tests/test_learn_late_edges_cpu.py, tests/test_hip_learn_perdqn_edges.py) ----
+EDGE_BATCHES = (64, 33, 1)
+_edge = None
+
+
+def edge_case():
+    """One step on the reference's TRAINED weights: (ckpt_perdqn_gene_1_weights of tests/golden/perdqn.npz, the same times
+    learn_cases.TARGET_SCALE as the target, learn_cases.edge_ring_rows(1027), the priorities learn_perd3qn_cases.edge_priorities(1027)
+    with their zeros replaced by p_new, the minibatches of 64, 33 and 1 rows RandomState(1..3).randint(0, 1027, n)).  Made once, read-only."""
+    global _edge
+    if _edge is None:
+        import learn_cases as lc
+        with np.load(os.path.join(ROOT, "tests", "golden", "perdqn.npz")) as z:
+            w = z["ckpt_perdqn_gene_1_weights"]
+        tgt = (w * lc.TARGET_SCALE).astype(np.float32)
+        rows = lc.edge_ring_rows(1027)
+        pri = pc.edge_priorities(1027).copy()
+        pri[pri == 0] = golden()["p_new"]
+        batches = [np.random.RandomState(1 + i).randint(0, 1027, n).astype(np.int32) for i, n in enumerate(EDGE_BATCHES)]
+        for a in [w, tgt, pri] + batches:
+            a.setflags(write=False)
+        _edge = (w, tgt, rows, pri, batches)
+    return _edge

@@ -222,3 +222,44 @@ def rollout_draw(keys_by_slot, window, salt):
     if not window:
         return 0
     return min(window, key=lambda i: (mix64(keys_by_slot[i] ^ salt), i))
+
+
+def rollout_table(keys, window, seed, brain, calls, n_draws):
+    """rollout_draw for every draw of a call at once, in numpy's integers: draw d takes the window slot with the smallest
+    (mix64(key ^ salt_d), slot), salt_d = words 0-1 of rl_philox(seed, 0, brain, calls, RL_SITE_LEARN_ROLLOUT, d); slot 0 from an empty
+    window -> int64 [n_draws].  keys: uint64 by slot."""
+    from reinlife_amd import _lib
+    import learn_perd3qn_cases as prio
+    if not len(window):
+        return np.zeros(n_draws, np.int64)
+    window = np.asarray(window, np.int64)
+    k = np.asarray(keys, np.uint64)[window]
+    out = np.zeros(n_draws, np.int64)
+    for d, salt in enumerate(prio._salts(seed, brain, calls, _lib.SITE_LEARN_ROLLOUT, n_draws)):
+        out[d] = window[np.lexsort((window, prio._mix64(k ^ salt)))[0]]
+    return out
+
+
+# ---- inputs beyond the fixture (tests/test_learn_late_edges_cpu.py, tests/test_hip_learn_ppo_edges.py) ----
+EDGE_FACTORS = np.array([1, 0.8, 1.25, 0.95, 1.05, 0.5, 2], np.float64)
+EDGE_ROLLOUT_ROWS = (32, 31, 17, 1)
+_edge = None
+
+
+def edge_case():
+    """One epoch on the reference's TRAINED weights: (PPO_weights of tests/golden/pretrained.npz, learn_cases.edge_ring_rows(1027), the
+    prob column float32(pi64(s)[a] / factor) with factor drawn by RandomState(5) from EDGE_FACTORS, the rollouts of 32, 31, 17 and 1
+    rows RandomState(1..4).randint(0, 1027, n)).  Made once, read-only."""
+    global _edge
+    if _edge is None:
+        import learn_cases as lc
+        w = lc.pretrained("PPO")[0]
+        rows = lc.edge_ring_rows(1027)
+        factor = np.random.RandomState(5).choice(EDGE_FACTORS, size=1027)
+        pi = outputs(w, rows["ring_state"])[np.arange(1027), rows["ring_action"].astype(np.int64)]
+        prob = (pi / factor).astype(np.float32)
+        rollouts = [np.random.RandomState(1 + i).randint(0, 1027, n).astype(np.int32) for i, n in enumerate(EDGE_ROLLOUT_ROWS)]
+        for a in [prob] + rollouts:
+            a.setflags(write=False)
+        _edge = (w, rows, prob, rollouts)
+    return _edge

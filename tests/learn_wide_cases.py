@@ -36,16 +36,29 @@ def slot_table(n_steps, batch, size, seed, equal_tile=None):
     return s
 
 
-def edge_case(batch, equal_tile=None):
-    """One step of the reference's trained DQN weights (target = weights * 0.96875) on lc.edge_ring_rows: (eval, target, rows, slots
-    [batch], float64 loss, the six float64 gradient tensors).  Computed once per case."""
-    key = (batch, equal_tile)
+def edge_case(batch, equal_tile=None, n_rows=EDGE_ROWS):
+    """One step of the reference's trained DQN weights (target = weights * 0.96875) on lc.edge_ring_rows(n_rows): (eval, target, rows,
+    slots [batch], float64 loss, the six float64 gradient tensors).  Computed once per case."""
+    key = (batch, equal_tile) if n_rows == EDGE_ROWS else (batch, equal_tile, n_rows)
     if key not in _ref:
         w, tgt = lc.pretrained("DQN")
-        rows = lc.edge_ring_rows(EDGE_ROWS)
-        slots = slot_table(1, batch, EDGE_ROWS, 100 + batch, equal_tile)[0]
+        rows = lc.edge_ring_rows(n_rows)
+        slots = slot_table(1, batch, n_rows, 100 + batch, equal_tile)[0]
         loss64, g64 = lc.grads64(w, tgt, rows, slots, GAMMA)
         for a in g64:
             a.setflags(write=False)
         _ref[key] = (w, tgt, rows, slots, loss64, g64)
     return _ref[key]
+
+
+def tile_loss_model(w, tgt, rows, slots, dtype=None):
+    """k_wide_tile's loss bookkeeping on the host: the smooth-L1 term of every batch row in float64, summed per 32-row tile, the tiles
+    summed in double and divided by the batch (k_wide_apply) -> (the loss, the tile sums [tiles])."""
+    import torch
+    with torch.no_grad():
+        td = lc.td_errors(lc.qnet(np.asarray(w, np.float64)), lc.qnet(np.asarray(tgt, np.float64)), rows, slots, GAMMA, torch.float64).numpy()[:, 0]
+    term = np.where(np.abs(td) < 1, 0.5 * td * td, np.abs(td) - 0.5)
+    pad = np.zeros(tiles(len(slots)) * TILE)
+    pad[:len(slots)] = term
+    per_tile = pad.reshape(-1, TILE).sum(1)
+    return float(per_tile.sum() / len(slots)), per_tile
