@@ -17,6 +17,8 @@
  *   rl_learn           DQNAgent.train(): the size gate, 5 minibatch updates (smooth-L1, Adam) and the target copy
  *                      Models/DQN.py:80-83, 142-153 (sampling: :99-113, with replacement here)
  *   rl_learn_wide      the same update on minibatches of up to 2048 rows, 32-row tiles side by side (DQN.py:80-83, 142-153)
+ *   rl_learn_draw_rank this build's own: the minibatch tables of rl_learn / rl_learn_wide / rl_learn_dueling drawn uniformly by the
+ *                      rows' content-key rank (one sort per call, one thread per draw)
  *   rl_learn_ppo       PPO.learn(): k_epoch full-batch Adam steps on a rollout of at most 32 rows (rl_learn_rollout draws it)
  *   rl_learn_dueling   D3QNAgent.train(): one minibatch update of the dueling network (MSE, Adam), batch up to 64
  *                      Models/D3QN.py:97-116, 148-165 (schedule and target copy of :118-126: the caller's)
@@ -385,7 +387,44 @@ int rl_learn_dueling(rl_world* h, const rl_learner* learners, const rl_replay* r
 int rl_learn_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps,
                   unsigned long long* const* keys, int32_t* slots, void* stream);
 
-/* ---- wide minibatches (DQN) -------------------------------------------------------------------------------------- */
+/* THIS BUILD'S OWN -- rl_learn_draw's table by another sampler: uniform draws by content-key RANK.  rl_learn_draw visits every key of a
+ * ring once per draw, so its cost grows with n_steps x batch x size; here the rows a ring holds are sorted by content key once per
+ * call and every draw is an index into that order, so the cost of a call does not depend on n_steps or the batches.  For learner i:
+ *   size     min(*ring.count, ring.capacity), read on the device
+ *   keys     host array [n_learners] of device uint64 [capacity]: keys[i][r], r < size, are the content keys exactly as rl_learn_draw
+ *            makes them, rewritten by every call
+ *   order    host array [n_learners] of device int32 [capacity]: after the call order[i][0 .. size) holds the slots 0 .. size - 1
+ *            ascending by (keys[slot], slot) -- numpy's lexsort((arange(size), keys[:size])).  Equal keys are equal rows up to a 2^-64
+ *            collision; the lower slot first makes the table a function of the ring's contents and layout, and the rows a draw names a
+ *            function of the contents alone.  Entries from `size` on are left as they were.
+ *   work     host array [n_learners] of device scratch of at least rl_learn_draw_rank_work_bytes(capacity) bytes each, 16-byte
+ *            aligned: two tables of 65,536 counters (the keys' top 16 bits name a bucket) and one int32 per ring row.  It needs no
+ *            initialisation and holds nothing between calls.
+ *   slots    device int32, the learners' flat [n_steps][batch] tables laid end to end, as for rl_learn_draw: draw d = s * batch + j,
+ *            d < n_steps * batch, takes x = word 0 of rl_philox(seed, 0, i, (uint32)state[1], RL_SITE_LEARN, d), t = ((uint64)x * size)
+ *            >> 32 and slots[d] = order[t] -- rl_learn's own slots == NULL mapping, applied to the rank instead of the slot: uniform up
+ *            to the multiply-shift's size / 2^32, WITH replacement.  size == 0 writes slot 0 for every draw.  batch is in
+ *            [1, RL_LEARN_WIDE_MAX] (the table is flat: no limit of 32 and no divisor trick), and the learners of a call may have
+ *            different batches.
+ * It is a DIFFERENT sampler from rl_learn_draw: the same distribution, other rows.  rl_learn_draw, rl_learn, rl_learn_wide and every
+ * *_supported answer are unchanged by it.
+ * RL_LEARN_DRAW_RANK_LAUNCHES (6) launches whatever n_steps, the batches and the rings hold, all queued on `stream`: clear the
+ * counters, keys and histogram (one wave per row), the prefix sum (one workgroup per learner), the scatter into buckets, the placement
+ * inside every bucket (a member's place is the number of members with a smaller (key, slot): the sum of the squared bucket sizes in all,
+ * about two visits per row on mixed keys, size^2 -- bounded, still exact -- where every row of a ring is the same), and one thread per
+ * draw.  No host read-back, no allocation.  The only atomics are integer adds and nothing the caller sees depends on the order they
+ * arrive in: keys, order and slots have the same bits in every run.
+ * Validated on the host before anything is launched, RL_E_INVALID naming the argument: a null handle, learners, rings, keys, order,
+ * work or slots; a null learner state, keys[i], order[i] or work[i]; n_learners in [1, RL_MAX_CAPTURE_BRAINS]; n_steps >= 1 (and
+ * n_steps times the batches below 2^31 draws); the batch range; rl_learn_draw's ring checks (the age column included). */
+#define RL_LEARN_DRAW_RANK_LAUNCHES 6
+/* The bytes of one learner's work buffer for a ring of `capacity` rows (a multiple of 16); 0, with rl_last_error set, for a capacity
+ * outside [1, 2^31). */
+size_t rl_learn_draw_rank_work_bytes(long long capacity);
+int rl_learn_draw_rank(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps,
+                       unsigned long long* const* keys, int32_t* const* order, void* const* work, int32_t* slots, void* stream);
+
+/* ---- wide minibatches (DQN)-------------------------------------------------------------------------------------- */
 /* THIS BUILD'S OWN -- the reference trains one world on minibatches of 32 (DQN.py:80-83, 142-153).  rl_learn_wide is that update on a
  * minibatch of 1 .. RL_LEARN_WIDE_MAX rows, split into 32-row tiles that run side by side, one workgroup per (learner, tile): a run of
  * many worlds appends far more rows per learning episode than 5 x 32, and rl_learn keeps one CU busy.  A call whose batch is at most 32

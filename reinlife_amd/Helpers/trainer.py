@@ -20,7 +20,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
             limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None, seed=0, rng=None, per_agent_api=False,
             fused=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
             learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
-            learn_td_priority=None, learn_ranks=None, learn_batch=None):
+            learn_td_priority=None, learn_ranks=None, learn_batch=None, learn_draw=None):
     """Extra keyword-only arguments: n_worlds / device / seed / rng / synthetic_agents / refill_below (Environment); per_agent_api=True makes the reference's literal
     per-agent get_action / learn calls; fused (default: True for rng="philox" without per_agent_api) runs the loop through
     Environment.run -- whole chunks of ticks per launch, ending where the Tracker closes an interval -- instead of three launches
@@ -109,7 +109,15 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     step on a minibatch of learn_batch rows, computed in 32-row tiles that run side by side (one workgroup per brain and tile) and
     summed in tile order in double -- the same bits in every run.  Draw, schedule, gate (1000 rows), gamma, loss and target copy are the
     DQN learners'; a call is 2 learn_steps + 3 launches instead of one.  learn_batch=32 gives the parameters learn_batch=None gives, bit
-    for bit.  The learning rate stays the brain's: a wider batch averages more rows per step, it does not take more steps."""
+    for bit.  The learning rate stays the brain's: a wider batch averages more rows per step, it does not take more steps.
+    learn_draw (default None: every run is launch for launch and bit for bit what it was; "rank" needs learn="device" and at least one
+    brain of the learning kinds -- one that rl_learn, rl_learn_wide or rl_learn_dueling trains -- anything else is a ValueError before a
+    device is touched): THIS BUILD'S OWN.  The DQN, wide DQN and D3QN learners' minibatches are then drawn by rl_learn_draw_rank instead of
+    rl_learn_draw: the rows a ring holds are sorted by content key once per call (ties: the lower slot) and draw d takes the row at rank
+    ((uint64)x_d * size) >> 32, x_d the draw's Philox word -- uniform with replacement and independent of the order the worlds appended
+    the rows in, as before, but ANOTHER sampler: other rows, other parameters.  Six launches per draw instead of two, at a cost that does
+    not grow with learn_steps x learn_batch (rl_learn_draw visits every key of a ring once per draw).  The prioritised, rollout and
+    PERDQN draws are untouched; learn_ranks="average" needs nothing (draws are rank-local)."""
     if learn == "device" and (per_agent_api or fused is False):
         raise ValueError("trainer(learn='device') needs the fused path (fused=True, per_agent_api=False): the replay rings are filled "
                          "inside the multi-tick launches")
@@ -120,7 +128,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
                       device=device, seed=seed, rng=rng, synthetic_agents=synthetic_agents, refill_below=refill_below, dist=dist,
                       world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps, learn_kinds=learn_kinds,
                       learn_prioritized=learn_prioritized, learn_rollout=learn_rollout, rollout_steps=rollout_steps,
-                      learn_td_priority=learn_td_priority, learn_ranks=learn_ranks, learn_batch=learn_batch)
+                      learn_td_priority=learn_td_priority, learn_ranks=learn_ranks, learn_batch=learn_batch, learn_draw=learn_draw)
     env.reset()
     if fused is None:
         fused = env.rng == "philox" and not per_agent_api

@@ -159,7 +159,7 @@ class Environment:
                  pastel_colors=False, limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None,
                  seed=0, rng=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
                  learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
-                 learn_td_priority=None, learn_ranks=None, learn_batch=None):
+                 learn_td_priority=None, learn_ranks=None, learn_batch=None, learn_draw=None):
         if not brains:
             raise ValueError("Environment needs a non-empty list of brains")
         if learn not in (None, "device"):
@@ -217,6 +217,17 @@ class Environment:
                 raise ValueError("learn_batch needs at least one Models.DQN brain among the learning kinds %r (got %s)"
                                  % (self.learn_kinds, ", ".join(str(getattr(b, "method", b)) for b in brains)))
         self.learn_batch = None if learn_batch is None else int(learn_batch)
+        # learn_draw="rank": the DQN, wide DQN and D3QN learners' minibatches are drawn by content-key rank (rl_learn_draw_rank: one sort
+        # per call, one thread per draw) instead of rl_learn_draw's minimum over all keys per draw -- another uniform sampler, so other
+        # rows: this build's own, an explicit opt-in.  None: rl_learn_draw, as always.  Checked before a device is touched.
+        if learn_draw not in (None, "rank"):
+            raise ValueError("learn_draw must be None (rl_learn_draw) or 'rank' (uniform draws by content-key rank, rl_learn_draw_rank), got %r" % (learn_draw,))
+        if learn_draw and learn != "device":
+            raise ValueError("learn_draw=%r needs learn='device' (got learn=%r)" % (learn_draw, learn))
+        if learn_draw and not any(getattr(b, "method", None) in self.learn_kinds for b in brains):
+            raise ValueError("learn_draw=%r needs at least one brain that rl_learn, rl_learn_wide or rl_learn_dueling trains: a brain of the "
+                             "learning kinds %r (got %s)" % (learn_draw, self.learn_kinds, ", ".join(str(getattr(b, "method", b)) for b in brains)))
+        self.learn_draw = learn_draw
         # learn_ranks="average": the ranks of a process group train independently and merge their learners at the end of every learn_now
         # (periodic parameter averaging; this build's own, the reference has no multi-process training).  Checked before a device is touched.
         if learn_ranks not in (None, "average"):
@@ -362,7 +373,7 @@ class Environment:
             if frozen:
                 warn_inference_only(frozen, self.learn_kinds + (("PERD3QN (prioritised)",) if self.learn_prioritized else ())
                                     + (("PPO (rollouts)",) if self.learn_rollout else ())
-                                    + (("PERDQN (TD priorities)",) if self.learn_td_priority else ()))
+                                    + (("PERDQN (TD priorities)",) if self.learn_td_priority else ()), draw=self.learn_draw)
             if self.learn_ranks:
                 self._align_learners()
         elif training:
@@ -683,6 +694,8 @@ class Environment:
                     "Weights": self._weights_note()}
         if self.learn_batch is not None:   # (extra key, only where the keyword was given)
             settings["Learn batch"] = self.learn_batch
+        if self.learn_draw is not None:    # (likewise)
+            settings["Learn draw"] = self.learn_draw
         if self.static_families:
             agents = [SavedAgent(g, b) for g, b in enumerate(self.brains)]
         else:  # the brains the best agents descend from (inference-time copies share their weights)
@@ -730,6 +743,10 @@ class Environment:
         if frozen:
             note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if (duel or prio or ppo or td) else
                         "brains %s as loaded / initialised (their kinds do not learn in this build)" % frozen)
+        if self.learn_draw == "rank" and (wide or dqn or duel):
+            note.append("the minibatches of brains %s drawn by content-key rank (learn_draw='rank', rl_learn_draw_rank: the ring's rows sorted by "
+                        "content key, draw d the row at rank (x_d * size) >> 32 -- uniform with replacement, other rows than rl_learn_draw names)"
+                        % sorted(wide + dqn + duel))
         if self.learn_ranks:
             note.append("%d rank(s) trained independently on their own rings and averaged params, adam_m and adam_v over the ranks with the "
                         "highest step count after every learning episode (learn_ranks='average': periodic parameter averaging, this build's own)"
@@ -758,15 +775,19 @@ class Environment:
         learn_batch=B: the DQN learners are wide ones (rl_learn_wide, minibatches of B rows in 32-row tiles side by side) and are called in
         the DQN learners' place, the same way: draw (draw_slots: the same flat table, so B = 32 trains on rl_learn's rows), then learn,
         learn_steps steps -- 2 learn_steps + 3 launches instead of one.
+        learn_draw="rank": the draw_slots calls above -- the DQN, wide DQN and D3QN learners' -- are draw_slots_rank calls (rl_learn_draw_rank,
+        six launches instead of two: the rings' rows sorted by content key once, every draw an index into that order); the prioritised,
+        rollout and PERDQN draws are what they are.
         learn_ranks="average": all of the above is rank-local and unchanged; the call then ends with the merge of ALL learners over the
         ranks (_merge_learners: one launch to export, ONE all-gather, two launches to merge) -- this build's own, periodic parameter
         averaging: D3QN, PERD3QN and PERDQN learners make one update per call from identical parameters and moments, so the merged
         result is the mean of the ranks' one-step Adam updates; DQN makes learn_steps local steps and PPO k_epoch per rollout in between."""
         self.learn_now_calls += 1
         called = []
+        draw_slots = self.worlds.draw_slots_rank if self.learn_draw == "rank" else self.worlds.draw_slots
         dqn = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry in ("rl_learn", "rl_learn_wide")]   # (learn_batch: all wide)
         if dqn:
-            self.worlds.learn(dqn, self.learn_steps, slots=self.worlds.draw_slots(dqn, self.learn_steps))
+            self.worlds.learn(dqn, self.learn_steps, slots=draw_slots(dqn, self.learn_steps))
             called += dqn
         duel = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_dueling"
                 and (last is None or last > self.learners[k].exploration)]
@@ -776,9 +797,9 @@ class Environment:
             if last is not None:
                 for l in ls:
                     l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
-            self.worlds.learn(ls, n, slots=self.worlds.draw_slots(ls, n))
+            self.worlds.learn(ls, n, slots=draw_slots(ls, n))
             called += ls
-        prio = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_prioritized"
+        prio =[self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_prioritized"
                 and (last is None or last > self.learners[k].exploration)]
         for batch in sorted({l.batch for l in prio}):
             ls = [l for l in prio if l.batch == batch]
@@ -949,17 +970,20 @@ def resolve_dist(dist=None):
     return None, 0, 1
 
 
-def warn_inference_only(frozen=None, kinds=("DQN",)):
+def warn_inference_only(frozen=None, kinds=("DQN",), draw=None):
     import warnings
     if frozen is not None:
+        # (a line more only where learn_draw was given: every other run's message is what it was)
+        drawn = "" if draw is None else "\nlearn_draw=%r draws the DQN / D3QN learners' minibatches by content-key rank (rl_learn_draw_rank)." % (draw,)
         if tuple(kinds) == ("DQN",):
             warnings.warn("learn='device' trains the DQN brains of this run; brains %s are of kinds rl_learn does not train yet: they stay "
                           "inference only -- brain.learn() is a no-op for them and their weights are NOT updated (D3QN brains learn with "
                           "learn_kinds=('DQN', 'D3QN'), PERD3QN brains with learn_prioritized=True, PPO brains with learn_rollout=True; PERDQN brains do "
-                          "not learn yet)." % ", ".join(frozen), stacklevel=3)
+                          "not learn yet)." % ", ".join(frozen) + drawn, stacklevel=3)
         else:
             warnings.warn("learn='device' trains the %s brains of this run; brains %s are of other kinds (or of kinds no entry point trains): they stay "
-                          "inference only -- brain.learn() is a no-op for them and their weights are NOT updated." % (" and ".join(kinds), ", ".join(frozen)), stacklevel=3)
+                          "inference only -- brain.learn() is a no-op for them and their weights are NOT updated." % (" and ".join(kinds), ", ".join(frozen)) + drawn,
+                          stacklevel=3)
         return
     warnings.warn("reinlife_amd runs ReinLife's per-tick path (world tick + policy inference) only: training=True keeps the "
                   "reference's loop, epsilon schedules and Tracker, but brain.learn() is a no-op and the brains' weights are NOT "

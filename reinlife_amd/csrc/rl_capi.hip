@@ -33,6 +33,8 @@ int rl_learn_draw_launch(rl_world*, const rl_learner*, const rl_replay*, int, in
 int rl_learn_wide_supported_impl(int);
 size_t rl_learn_wide_work_bytes_impl(int);
 int rl_learn_wide_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, const int32_t*, void* const*, hipStream_t);
+size_t rl_learn_draw_rank_work_bytes_impl(long long);
+int rl_learn_draw_rank_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, unsigned long long* const*, int32_t* const*, void* const*, int32_t*, hipStream_t);
 int rl_learn_dueling_supported_impl(int);
 int rl_learn_dueling_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, const int32_t*, hipStream_t);
 int rl_learn_prioritized_supported_impl(int);
@@ -496,6 +498,40 @@ int rl_learn_draw(rl_world* h, const rl_learner* learners, const rl_replay* ring
     }
     DeviceGuard guard(device_of_pointer(slots));
     return rl_learn_draw_launch(h, learners, rings, n_learners, n_steps, keys, slots, (hipStream_t)stream);
+}
+
+size_t rl_learn_draw_rank_work_bytes(long long capacity)
+{
+    if (capacity < 1 || capacity > 0x7fffffff) { rl_set_error("rl_learn_draw_rank_work_bytes: capacity must be in [1, 2^31) (got %lld)", capacity); return 0; }
+    return rl_learn_draw_rank_work_bytes_impl(capacity);
+}
+
+int rl_learn_draw_rank(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps,
+                       unsigned long long* const* keys, int32_t* const* order, void* const* work, int32_t* slots, void* stream)
+{
+    if (!h) { rl_set_error("rl_learn_draw_rank: null handle"); return RL_E_INVALID; }
+    if (!learners) { rl_set_error("rl_learn_draw_rank: null learners"); return RL_E_INVALID; }
+    if (!rings) { rl_set_error("rl_learn_draw_rank: null rings"); return RL_E_INVALID; }
+    if (!keys) { rl_set_error("rl_learn_draw_rank: null keys"); return RL_E_INVALID; }
+    if (!order) { rl_set_error("rl_learn_draw_rank: null order"); return RL_E_INVALID; }
+    if (!work) { rl_set_error("rl_learn_draw_rank: null work"); return RL_E_INVALID; }
+    if (!slots) { rl_set_error("rl_learn_draw_rank: null slots"); return RL_E_INVALID; }
+    if (n_learners < 1 || n_learners > RL_MAX_CAPTURE_BRAINS) { rl_set_error("rl_learn_draw_rank: n_learners must be in [1,%d] (got %d)", RL_MAX_CAPTURE_BRAINS, n_learners); return RL_E_INVALID; }
+    if (n_steps < 1) { rl_set_error("rl_learn_draw_rank: n_steps must be >= 1 (got %d)", n_steps); return RL_E_INVALID; }
+    long long draws = 0;
+    for (int i = 0; i < n_learners; ++i) {
+        const rl_replay& r = rings[i];
+        if (!learners[i].state) { rl_set_error("rl_learn_draw_rank: learner %d: state must not be null", i); return RL_E_INVALID; }
+        if (!keys[i]) { rl_set_error("rl_learn_draw_rank: keys[%d] must not be null", i); return RL_E_INVALID; }
+        if (!order[i]) { rl_set_error("rl_learn_draw_rank: order[%d] must not be null", i); return RL_E_INVALID; }
+        if (!work[i]) { rl_set_error("rl_learn_draw_rank: work[%d] must not be null (rl_learn_draw_rank_work_bytes)", i); return RL_E_INVALID; }
+        if (learners[i].batch < 1 || learners[i].batch > RL_LEARN_WIDE_MAX) { rl_set_error("rl_learn_draw_rank: learner %d: batch must be in [1,%d] (got %d)", i, RL_LEARN_WIDE_MAX, learners[i].batch); return RL_E_INVALID; }
+        if (!r.state || !r.state_prime || !r.action || !r.reward || !r.done || !r.age || !r.count || r.capacity < 1 || r.capacity > 0x7fffffff) { rl_set_error("rl_learn_draw_rank: replay %d incomplete (state / state_prime / action / reward / done / age / count, capacity in [1, 2^31))", i); return RL_E_INVALID; }
+        draws += (long long)n_steps * learners[i].batch;
+    }
+    if (draws > 0x7fffffff) { rl_set_error("rl_learn_draw_rank: n_steps times the learners' batches must stay below 2^31 draws (got %lld)", draws); return RL_E_INVALID; }
+    DeviceGuard guard(device_of_pointer(slots));
+    return rl_learn_draw_rank_launch(h, learners, rings, n_learners, n_steps, keys, order, work, slots, (hipStream_t)stream);
 }
 
 int rl_learn_prioritized_supported(int kind) { return rl_learn_prioritized_supported_impl(kind); }

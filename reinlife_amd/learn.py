@@ -147,6 +147,7 @@ class DeviceLearner:
         self.work = None          # wide_batch: rl_learn_wide's scratch (header, the tiles' partial gradients and loss sums); needs no initialisation
         if self.entry == "rl_learn_wide":
             self.work = torch.empty(int(lib.rl_learn_wide_work_bytes(self.kind, self.batch)), dtype=torch.uint8, device=self.device)
+        self.rank_order = self.rank_work = None   # DeviceWorlds.draw_slots_rank: the ring's slots in key order, and rl_learn_draw_rank's scratch
         self.loss = None          # optional device float32 [n_steps]
         self.grad = None          # optional device float32 [n_steps, n_params] (tests, diagnostics)
 

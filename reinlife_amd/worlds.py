@@ -444,6 +444,36 @@ class DeviceWorlds:
         self.launches += 2
         return slots
 
+    def draw_slots_rank(self, learners, n_steps):
+        """draw_slots() by another sampler (rl_learn_draw_rank, this build's own): every ring's rows are sorted by content key once and
+        draw d takes the row at rank ((uint64)x * size) >> 32, x = word 0 of rl_philox(seed, 0, i, calls, RL_SITE_LEARN, d) -- uniform,
+        with replacement, the same rows whatever slots they sit in, at a cost that does not depend on n_steps or the batch (draw_slots
+        visits every key of a ring once per draw).  Other rows than draw_slots names.  Device int32 [len(learners), n_steps, batch]
+        (batch 1 .. 2048, asked for as it is), queued on the current stream.  Keeps learner.keys, learner.rank_order (the slots in key
+        order, [0, size) defined) and learner.rank_work (scratch) on the learners, allocated once per ring size."""
+        n = len(learners)
+        if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
+            raise ValueError("draw_slots_rank(): 1 to %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
+        if len({l.batch for l in learners}) != 1:
+            raise ValueError("draw_slots_rank(): the learners of a call must share one batch size")
+        for l in learners:
+            capacity = int(l.ring["state"].shape[0])
+            if getattr(l, "keys", None) is None or l.keys.numel() != capacity:
+                l.keys = torch.zeros(capacity, dtype=torch.int64, device=self.device)
+            if getattr(l, "rank_order", None) is None or l.rank_order.numel() != capacity:
+                l.rank_order = torch.zeros(capacity, dtype=torch.int32, device=self.device)
+                l.rank_work = torch.empty(int(self.lib.rl_learn_draw_rank_work_bytes(capacity)), dtype=torch.uint8, device=self.device)
+        arr = (_lib.Learner * n)(*[l.struct() for l in learners])
+        rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
+        keys = (C.c_void_p * n)(*[l.keys.data_ptr() for l in learners])
+        order = (C.c_void_p * n)(*[l.rank_order.data_ptr() for l in learners])
+        work = (C.c_void_p * n)(*[l.rank_work.data_ptr() for l in learners])
+        slots = torch.zeros((n, int(n_steps), int(learners[0].batch)), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.rl_learn_draw_rank(self.handle, arr, rings, n, int(n_steps), keys, order, work, _ptr(slots), self._stream()),
+                   "rl_learn_draw_rank")
+        self.launches += _lib.LEARN_DRAW_RANK_LAUNCHES
+        return slots
+
     def draw_prioritized(self, learners, n_steps):
         """The minibatches of prioritised learners (DeviceLearner(..., prioritized=True)) for learn(learners, n_steps, slots=...):
         PrioritizedReplayBuffer.sample's draw (PERD3QN.py:157-165) on the device (rl_learn_prioritized_draw) -- first every row appended
