@@ -17,6 +17,7 @@
  *   rl_learn           DQNAgent.train(): the size gate, 5 minibatch updates (smooth-L1, Adam) and the target copy
  *                      Models/DQN.py:80-83, 142-153 (sampling: :99-113, with replacement here)
  *   rl_learn_wide      the same update on minibatches of up to 2048 rows, 32-row tiles side by side (DQN.py:80-83, 142-153)
+ *   rl_learn_dueling_wide  D3QNAgent.train() on minibatches of up to 2048 rows, 64-row tiles side by side, the batch-wide mean kept
  *   rl_learn_draw_rank this build's own: the minibatch tables of rl_learn / rl_learn_wide / rl_learn_dueling drawn uniformly by the
  *                      rows' content-key rank (one sort per call, one thread per draw)
  *   rl_learn_ppo       PPO.learn(): k_epoch full-batch Adam steps on a rollout of at most 32 rows (rl_learn_rollout draws it)
@@ -461,6 +462,53 @@ size_t rl_learn_wide_work_bytes(int kind, int batch);
  * equal for all learners, rl_learn's null-pointer and capacity checks, a null work[i]. */
 int rl_learn_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, const int32_t* slots,
                   void* const* work, void* stream);
+
+/* ---- wide minibatches (D3QN) ------------------------------------------------------------------------------------- */
+/* THIS BUILD'S OWN -- the reference trains one world on ONE minibatch of 64 per train() (D3QN.py:97-116).  rl_learn_dueling_wide is that
+ * update on a minibatch of 1 .. RL_LEARN_DUELING_WIDE_MAX rows, split into 64-row tiles that run side by side, one workgroup per (learner,
+ * tile), with dueling_ddqn.forward's advantage mean (D3QN.py:165) taken over the WHOLE minibatch as the reference takes it: the tiles
+ * meet in three scalars per step (the two means and the sum of the rows' loss gradients), each a sum of per-tile sums in tile order.  A
+ * call whose batch is at most 64 (one tile) leaves every buffer bit for bit as rl_learn_dueling leaves it.  rl_learn_dueling and every
+ * other entry point are unchanged by it. */
+#define RL_LEARN_DUELING_WIDE_MAX 2048
+/* 1 for the brain kinds rl_learn_dueling_wide trains (RL_D3QN), 0 for the others (RL_PERD3QN: its prioritised memory is not kept here) */
+int rl_learn_dueling_wide_supported(int kind);
+/* The bytes of one learner's work buffer for a minibatch of `batch` rows, T = ceil(batch / 64): a 64-byte header, T rows of
+ * rl_policy_n_params(kind) floats (the tiles' partial gradients), 2 T floats rounded up to 16 bytes (the tiles' advantage sums) and
+ * T x 64 rows of 14 floats (per row adv'[8], val', adv[a], val, reward, mask, action).  0, with rl_last_error set, for a kind
+ * rl_learn_dueling_wide does not train or a batch outside [1, RL_LEARN_DUELING_WIDE_MAX]. */
+size_t rl_learn_dueling_wide_work_bytes(int kind, int batch);
+/* D3QNAgent.train() (D3QN.py:97-116) on wide minibatches for n_learners brains, on the rl_learner / rl_replay structures of
+ * rl_learn_dueling (kind must be RL_D3QN: anything else is RL_E_UNSUPPORTED naming the kind; batch in [1, RL_LEARN_DUELING_WIDE_MAX],
+ * ONE batch for all learners of a call).
+ *   work        host array [n_learners] of device buffers of at least rl_learn_dueling_wide_work_bytes(kind, batch) bytes each, 16-byte
+ *               aligned; they need no initialisation and hold nothing between calls
+ *   size gate   as rl_learn_dueling: size = min(*ring.count, ring.capacity), read on the device; size <= min_size: no update
+ *   rows        slots != NULL: device int32 [n_learners][n_steps][batch]; every entry of a learner that trains is range-checked
+ *               before a row is fetched -- a bad one sets error-flag code 6 ([1] = learner, [2] = step, [3] = the value; the first in
+ *               table order) and that learner leaves the call with NONE of its buffers touched (the others train).  slots == NULL:
+ *               rl_learn_dueling's draw with the wider batch: slot = ((uint64)x * size) >> 32, x = word 0 of rl_philox(seed, 0, i,
+ *               (uint32)state[1], RL_SITE_LEARN, s * batch + j).  Tile t of a step holds batch rows 64 t .. min(64 t + 63, batch - 1).
+ *   a step      first pass, every tile: rl_learn_dueling's target forward on s' and eval forward on s; per tile the f32 sums of its live
+ *               rows' advantage sums (row ascending), per row a few numbers, to `work`.  Second pass, every tile, identically: M' and M =
+ *               (float)(the tiles' sums added in double, tile ascending) / (float)(8 batch); rl_learn_dueling's td and g_i = (2 td) *
+ *               (1.0f / batch) for every row of the batch; G and the loss from per-tile f32 sums (row ascending) added in double in tile
+ *               order and rounded once; then the tile's eval forward again and rl_learn_dueling's backward pass with G / (float)(8 batch),
+ *               its partial gradient (per parameter the f32 sum over the tile's rows, ascending) to `work`.  Then one thread per
+ *               parameter adds the tiles' partials in tile order in double, rounds to float once -- with one tile: the partial itself --
+ *               and makes rl_learn_dueling's Adam update.  loss[s] = (float)(that double sum of td^2) * (1.0f / batch); grad[s] = the
+ *               summed gradient.
+ *   afterwards  as rl_learn_dueling: sync_target != 0: target <- params (also below the size gate); state[0] += updates made;
+ *               state[1] += 1; `packed` rewritten from the final params, bit for bit what rl_policy_pack_weights(RL_D3QN, ...) makes.
+ * 3 n_steps + 3 launches, all queued on `stream`: one check pass (gate, slots, header), per step the two tile passes and the update, one
+ * pass for target and counters, one for `packed`.  No host read-back, no cooperative launch, no workgroup waits for another, no
+ * allocation.  Deterministic: every sum has a fixed order and no float atomics exist, so the same buffers give the same bits in every
+ * run and whatever else is in the launch.
+ * Validated on the host before anything is launched, RL_E_INVALID naming the argument: null handle / learners / rings / work,
+ * n_learners in [1, RL_MAX_CAPTURE_BRAINS], n_steps >= 1, batch in [1, RL_LEARN_DUELING_WIDE_MAX] and equal for all learners,
+ * rl_learn's null-pointer and capacity checks, a null work[i]. */
+int rl_learn_dueling_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps,
+                          const int32_t* slots, void* const* work, void* stream);
 
 /* ---- prioritised replay (PERD3QN) ------------------------------------------------------------------------------- */
 /* The prioritised memory of one learning PERD3QN brain (PrioritizedReplayBuffer, Models/PERD3QN.py:133-182) beside its rl_replay ring:

@@ -110,6 +110,14 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     summed in tile order in double -- the same bits in every run.  Draw, schedule, gate (1000 rows), gamma, loss and target copy are the
     DQN learners'; a call is 2 learn_steps + 3 launches instead of one.  learn_batch=32 gives the parameters learn_batch=None gives, bit
     for bit.  The learning rate stays the brain's: a wider batch averages more rows per step, it does not take more steps.
+    learn_batch also takes a dict by kind, like learn_steps: {"DQN": B}, {"D3QN": B} or both (keys from these two, at least one; ints in
+    [1, 2048]; a named kind must be among learn_kinds and have a brain in the list: ValueError otherwise, before a device is touched).
+    "D3QN" (this build's own -- the reference's minibatch is 64 rows, D3QN.py:98): every D3QN learner trains through
+    rl_learn_dueling_wide, each update one Adam step on a minibatch of B rows computed in 64-row tiles side by side, with
+    dueling_ddqn.forward's advantage mean (D3QN.py:165) taken over the WHOLE minibatch as the reference takes it -- the tiles meet in
+    three scalars per step, summed in tile order in double, the same bits in every run.  Schedule, gate (exploration, a ring of at least
+    batch_size rows), learn_steps per kind, target sync rule, learning rate, learn_draw and learn_ranks are the D3QN learners'; a call is
+    3 learn_steps["D3QN"] + 3 launches instead of one.  {"D3QN": 64} gives the learners that learn_kinds alone gives, bit for bit.
     learn_draw (default None: every run is launch for launch and bit for bit what it was; "rank" needs learn="device" and at least one
     brain of the learning kinds -- one that rl_learn, rl_learn_wide or rl_learn_dueling trains -- anything else is a ValueError before a
     device is touched): THIS BUILD'S OWN.  The DQN, wide DQN and D3QN learners' minibatches are then drawn by rl_learn_draw_rank instead of

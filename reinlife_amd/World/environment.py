@@ -207,7 +207,27 @@ class Environment:
         self.learn_td_priority = bool(learn_td_priority)
         # learn_batch=B: every DQN learner trains through rl_learn_wide on minibatches of B rows (1 .. 2048) in 32-row tiles side by side
         # (this build's own: the reference's minibatch is 32, DQN.py:16).  None: rl_learn, as always.  Checked before a device is touched.
-        if learn_batch is not None:
+        # A dict by kind, like learn_steps: {"DQN": B}, {"D3QN": B} or both -- "D3QN": every D3QN learner trains through rl_learn_dueling_wide
+        # on minibatches of B rows in 64-row tiles, the advantage mean taken over the whole batch (the reference's minibatch is 64, D3QN.py:98).
+        self.learn_batch_of = {"DQN": None, "D3QN": None}
+        if isinstance(learn_batch, dict):
+            limits = {"DQN": _lib.LEARN_WIDE_MAX, "D3QN": _lib.LEARN_DUELING_WIDE_MAX}
+            unknown = [k for k in learn_batch if k not in limits]
+            if unknown or not learn_batch:
+                raise ValueError("learn_batch as a dict takes the keys 'DQN' (rl_learn_wide) and 'D3QN' (rl_learn_dueling_wide) and at least one of them, got %r"
+                                 % (learn_batch,))
+            for k, v in learn_batch.items():
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= limits[k]:
+                    raise ValueError("learn_batch[%r] must be an int in [1, %d] (the rows of a %s minibatch, %s), got %r"
+                                     % (k, limits[k], k, "rl_learn_wide" if k == "DQN" else "rl_learn_dueling_wide", v))
+            if learn != "device":
+                raise ValueError("learn_batch needs learn='device' (got learn=%r)" % (learn,))
+            for k in learn_batch:
+                if k not in self.learn_kinds or not any(getattr(b, "method", None) == k for b in brains):
+                    raise ValueError("learn_batch names %s: it needs at least one Models.%s brain among the learning kinds %r (got %s)"
+                                     % (k, k, self.learn_kinds, ", ".join(str(getattr(b, "method", b)) for b in brains)))
+            self.learn_batch_of.update({k: int(v) for k, v in learn_batch.items()})
+        elif learn_batch is not None:
             if isinstance(learn_batch, bool) or not isinstance(learn_batch, (int, np.integer)) or not 1 <= learn_batch <= _lib.LEARN_WIDE_MAX:
                 raise ValueError("learn_batch must be None or an int in [1, %d] (the rows of a DQN minibatch, rl_learn_wide), got %r"
                                  % (_lib.LEARN_WIDE_MAX, learn_batch))
@@ -216,7 +236,9 @@ class Environment:
             if "DQN" not in self.learn_kinds or not any(getattr(b, "method", None) == "DQN" for b in brains):
                 raise ValueError("learn_batch needs at least one Models.DQN brain among the learning kinds %r (got %s)"
                                  % (self.learn_kinds, ", ".join(str(getattr(b, "method", b)) for b in brains)))
-        self.learn_batch = None if learn_batch is None else int(learn_batch)
+            self.learn_batch_of["DQN"] = int(learn_batch)
+        # (what the caller gave: the int it always was, None, or a plain dict copy; learn_batch_of is what the learners are built from)
+        self.learn_batch = {k: int(v) for k, v in learn_batch.items()} if isinstance(learn_batch, dict) else None if learn_batch is None else int(learn_batch)
         # learn_draw="rank": the DQN, wide DQN and D3QN learners' minibatches are drawn by content-key rank (rl_learn_draw_rank: one sort
         # per call, one thread per draw) instead of rl_learn_draw's minimum over all keys per draw -- another uniform sampler, so other
         # rows: this build's own, an explicit opt-in.  None: rl_learn_draw, as always.  Checked before a device is touched.
@@ -351,7 +373,8 @@ class Environment:
             else:
                 self.worlds.enable_capture(BUFFER_LIMIT, **prob)
             for k in entries:
-                wide = {"wide_batch": self.learn_batch} if self.learn_batch is not None and entries[k] == "rl_learn" else {}
+                wide = ({"wide_batch": self.learn_batch_of["DQN"]} if self.learn_batch_of["DQN"] is not None and entries[k] == "rl_learn" else
+                        {"dueling_batch": self.learn_batch_of["D3QN"]} if self.learn_batch_of["D3QN"] is not None and entries[k] == "rl_learn_dueling" else {})
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], **wide)
             for k in prio:
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], prioritized=True)
@@ -389,12 +412,12 @@ class Environment:
             return
         from ..distributed import broadcast_from_rank0, check_learner_signature
         ls = [self.learners[k] for k in sorted(self.learners)]
-        entries = ("rl_learn", "rl_learn_dueling", "rl_learn_prioritized", "rl_learn_ppo", "rl_learn_td", "rl_learn_wide")
+        entries = ("rl_learn", "rl_learn_dueling", "rl_learn_prioritized", "rl_learn_ppo", "rl_learn_td", "rl_learn_wide", "rl_learn_dueling_wide")
         sig = [len(ls)]
         for k in sorted(self.learners):
             l = self.learners[k]   # (exploration and soft_update_freq decide whether a learner is called and when its target is synced)
             sig += [k, l.kind, entries.index(l.entry), getattr(l, "exploration", 0), getattr(l, "soft_update_freq", 0)]
-            if l.entry == "rl_learn_wide":   # (the other entry points' batches come from the brains' classes: the signatures of runs without learn_batch stay what they were)
+            if l.entry in ("rl_learn_wide", "rl_learn_dueling_wide"):   # (the other entry points' batches come from the brains' classes: the signatures of runs without learn_batch stay what they were)
                 sig += [l.batch]
         sig += [self.learn_every, self.learn_steps_of["DQN"], self.learn_steps_of["D3QN"], self.learn_steps_of["PERDQN"], self.rollout_steps]
         check_learner_signature(sig, self.dist, device=self.worlds.device)
@@ -711,10 +734,16 @@ class Environment:
         duel = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_dueling")
         prio = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_prioritized")
         wide = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_wide")
+        dwide = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_dueling_wide")
         note = []
         if wide:
             note.append("brains %s trained on the device (rl_learn_wide: %d minibatch updates of batch %d (learn_batch) every %d episodes, rows drawn by "
-                        "content key with replacement)" % (wide, self.learn_steps, self.learn_batch, self.learn_every))
+                        "content key with replacement)" % (wide, self.learn_steps, self.learn_batch_of["DQN"], self.learn_every))
+        if dwide:
+            note.append("brains %s trained on the device (rl_learn_dueling_wide: %d minibatch update(s) of batch %d (learn_batch) in 64-row tiles, the "
+                        "advantage mean taken over the whole batch, every %d episodes once past the brain's exploration, target synced every "
+                        "soft_update_freq episodes, rows drawn by content key with replacement)"
+                        % (dwide, self.learn_steps_of["D3QN"], self.learn_batch_of["D3QN"], self.learn_every))
         if dqn:
             note.append("brains %s trained on the device (rl_learn: %d minibatch updates every %d episodes, rows drawn by content key with replacement)"
                         % (dqn, self.learn_steps, self.learn_every))
@@ -743,10 +772,10 @@ class Environment:
         if frozen:
             note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if (duel or prio or ppo or td) else
                         "brains %s as loaded / initialised (their kinds do not learn in this build)" % frozen)
-        if self.learn_draw == "rank" and (wide or dqn or duel):
+        if self.learn_draw == "rank" and (wide or dqn or duel or dwide):
             note.append("the minibatches of brains %s drawn by content-key rank (learn_draw='rank', rl_learn_draw_rank: the ring's rows sorted by "
                         "content key, draw d the row at rank (x_d * size) >> 32 -- uniform with replacement, other rows than rl_learn_draw names)"
-                        % sorted(wide + dqn + duel))
+                        % sorted(wide + dqn + duel + dwide))
         if self.learn_ranks:
             note.append("%d rank(s) trained independently on their own rings and averaged params, adam_m and adam_v over the ranks with the "
                         "highest step count after every learning episode (learn_ranks='average': periodic parameter averaging, this build's own)"
@@ -775,6 +804,9 @@ class Environment:
         learn_batch=B: the DQN learners are wide ones (rl_learn_wide, minibatches of B rows in 32-row tiles side by side) and are called in
         the DQN learners' place, the same way: draw (draw_slots: the same flat table, so B = 32 trains on rl_learn's rows), then learn,
         learn_steps steps -- 2 learn_steps + 3 launches instead of one.
+        learn_batch={"D3QN": B}: the D3QN learners are wide ones (rl_learn_dueling_wide, minibatches of B rows in 64-row tiles side by side,
+        the advantage mean of the whole batch) and are called in the D3QN learners' place, the same way -- schedule, gate, draw, target
+        rule --, 3 learn_steps["D3QN"] + 3 launches instead of one; B = 64 trains on rl_learn_dueling's rows and ends with its bits.
         learn_draw="rank": the draw_slots calls above -- the DQN, wide DQN and D3QN learners' -- are draw_slots_rank calls (rl_learn_draw_rank,
         six launches instead of two: the rings' rows sorted by content key once, every draw an index into that order); the prioritised,
         rollout and PERDQN draws are what they are.
@@ -789,7 +821,7 @@ class Environment:
         if dqn:
             self.worlds.learn(dqn, self.learn_steps, slots=draw_slots(dqn, self.learn_steps))
             called += dqn
-        duel = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_dueling"
+        duel = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry in ("rl_learn_dueling", "rl_learn_dueling_wide")   # (learn_batch naming D3QN: all wide)
                 and (last is None or last > self.learners[k].exploration)]
         n = self.learn_steps_of["D3QN"]
         for batch in sorted({l.batch for l in duel}):   # (one call per batch size: a call's slot table is rectangular)

@@ -90,6 +90,7 @@ SITE_LEARN_TD = 13       # RL_SITE_LEARN_TD: the Philox site of rl_learn_td_draw
 MAX_CAPTURE_BRAINS = 16  # RL_MAX_CAPTURE_BRAINS
 MAX_MERGE_RANKS = 64     # rl_learn_merge: n_ranks at most
 LEARN_WIDE_MAX = 2048    # RL_LEARN_WIDE_MAX: the rows of a minibatch at most (rl_learn_wide)
+LEARN_DUELING_WIDE_MAX = 2048   # RL_LEARN_DUELING_WIDE_MAX: the rows of a minibatch at most (rl_learn_dueling_wide)
 LEARN_DRAW_RANK_LAUNCHES = 6   # RL_LEARN_DRAW_RANK_LAUNCHES: the launches of one rl_learn_draw_rank call
 PPO_ROLLOUT_MAX = 32    # RL_PPO_ROLLOUT_MAX: the rows of a rollout at most (rl_learn_ppo)
 
@@ -136,6 +137,9 @@ ABI = [
     ("rl_learn_wide", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, _P, C.POINTER(_P), _P]),
     ("rl_learn_dueling_supported", C.c_int, [C.c_int]),
     ("rl_learn_dueling", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_dueling_wide_supported", C.c_int, [C.c_int]),
+    ("rl_learn_dueling_wide_work_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("rl_learn_dueling_wide", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, _P, C.POINTER(_P), _P]),
     ("rl_learn_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, C.POINTER(_P), _P, _P]),
     ("rl_learn_draw_rank_work_bytes", C.c_size_t, [C.c_longlong]),
     ("rl_learn_draw_rank", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.c_int, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),

@@ -7,7 +7,7 @@
 
 #include "rl_common.h"
 
-// implemented in rl_world.hip / rl_policy.hip / rl_render.hip / rl_learn.hip / rl_learn_dueling.hip / rl_learn_prio.hip / rl_learn_td.hip / rl_learn_merge.hip / rl_learn_wide.hip
+// implemented in rl_world.hip / rl_policy.hip / rl_render.hip / rl_learn.hip / rl_learn_dueling.hip / rl_learn_prio.hip / rl_learn_td.hip / rl_learn_merge.hip / rl_learn_wide.hip / rl_learn_dueling_wide.hip
 size_t rl_world_smem_bytes(int cpad, int cap, int hash, int plane_stride, int height);
 int rl_world_block();
 int rl_world_launch_step(rl_world*, const int8_t*, const rl_tape*, const rl_step_out*, hipStream_t);
@@ -35,6 +35,9 @@ size_t rl_learn_wide_work_bytes_impl(int);
 int rl_learn_wide_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, const int32_t*, void* const*, hipStream_t);
 size_t rl_learn_draw_rank_work_bytes_impl(long long);
 int rl_learn_draw_rank_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, unsigned long long* const*, int32_t* const*, void* const*, int32_t*, hipStream_t);
+int rl_learn_dueling_wide_supported_impl(int);
+size_t rl_learn_dueling_wide_work_bytes_impl(int);
+int rl_learn_dueling_wide_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, const int32_t*, void* const*, hipStream_t);
 int rl_learn_dueling_supported_impl(int);
 int rl_learn_dueling_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, const int32_t*, hipStream_t);
 int rl_learn_prioritized_supported_impl(int);
@@ -481,6 +484,37 @@ int rl_learn_dueling(rl_world* h, const rl_learner* learners, const rl_replay* r
     }
     DeviceGuard guard(device_of_pointer(learners[0].params));
     return rl_learn_dueling_launch(h, learners, rings, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+int rl_learn_dueling_wide_supported(int kind) { return rl_learn_dueling_wide_supported_impl(kind); }
+
+size_t rl_learn_dueling_wide_work_bytes(int kind, int batch)
+{
+    if (!rl_learn_dueling_wide_supported_impl(kind)) { rl_set_error("rl_learn_dueling_wide_work_bytes: brain kind %d; rl_learn_dueling_wide trains RL_D3QN (1) only (rl_learn_dueling_wide_supported)", kind); return 0; }
+    if (batch < 1 || batch > RL_LEARN_DUELING_WIDE_MAX) { rl_set_error("rl_learn_dueling_wide_work_bytes: batch must be in [1,%d] (got %d)", RL_LEARN_DUELING_WIDE_MAX, batch); return 0; }
+    return rl_learn_dueling_wide_work_bytes_impl(batch);
+}
+
+int rl_learn_dueling_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, const int32_t* slots,
+                          void* const* work, void* stream)
+{
+    if (!h) { rl_set_error("rl_learn_dueling_wide: null handle"); return RL_E_INVALID; }
+    if (!learners || !rings) { rl_set_error("rl_learn_dueling_wide: null learners / rings"); return RL_E_INVALID; }
+    if (!work) { rl_set_error("rl_learn_dueling_wide: null work"); return RL_E_INVALID; }
+    if (n_learners < 1 || n_learners > RL_MAX_CAPTURE_BRAINS) { rl_set_error("rl_learn_dueling_wide: n_learners must be in [1,%d] (got %d)", RL_MAX_CAPTURE_BRAINS, n_learners); return RL_E_INVALID; }
+    if (n_steps < 1) { rl_set_error("rl_learn_dueling_wide: n_steps must be >= 1 (got %d)", n_steps); return RL_E_INVALID; }
+    for (int i = 0; i < n_learners; ++i) {
+        const rl_learner& l = learners[i];
+        const rl_replay& r = rings[i];
+        if (!rl_learn_dueling_wide_supported_impl(l.kind)) { rl_set_error("rl_learn_dueling_wide: learner %d has brain kind %d; this entry point trains RL_D3QN (1) only (rl_learn_dueling_wide_supported; a PERD3QN brain's prioritised memory is not kept here)", i, l.kind); return RL_E_UNSUPPORTED; }
+        if (!l.params || !l.target || !l.adam_m || !l.adam_v || !l.state || !l.packed) { rl_set_error("rl_learn_dueling_wide: learner %d: params / target / adam_m / adam_v / state / packed must not be null", i); return RL_E_INVALID; }
+        if (l.batch < 1 || l.batch > RL_LEARN_DUELING_WIDE_MAX) { rl_set_error("rl_learn_dueling_wide: learner %d: batch must be in [1,%d] (got %d)", i, RL_LEARN_DUELING_WIDE_MAX, l.batch); return RL_E_INVALID; }
+        if (l.batch != learners[0].batch) { rl_set_error("rl_learn_dueling_wide: learner %d: batch %d differs from learner 0's %d (the learners of a call share one batch)", i, l.batch, learners[0].batch); return RL_E_INVALID; }
+        if (!r.state || !r.state_prime || !r.action || !r.reward || !r.done || !r.count || r.capacity < 1 || r.capacity > 0x7fffffff) { rl_set_error("rl_learn_dueling_wide: replay %d incomplete (state / state_prime / action / reward / done / count, capacity in [1, 2^31))", i); return RL_E_INVALID; }
+        if (!work[i]) { rl_set_error("rl_learn_dueling_wide: work[%d] must not be null (rl_learn_dueling_wide_work_bytes)", i); return RL_E_INVALID; }
+    }
+    DeviceGuard guard(device_of_pointer(learners[0].params));
+    return rl_learn_dueling_wide_launch(h, learners, rings, n_learners, n_steps, slots, work, (hipStream_t)stream);
 }
 
 int rl_learn_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps, unsigned long long* const* keys,

@@ -83,7 +83,7 @@ SIGNATURE_LEN = 128   # numbers of a learner signature at most: every rank gathe
 def check_learner_signature(signature, dist, device=None):
     """Set-up of learn_ranks="average": every rank must hold the same learners on the same schedule, or the per-episode all-gather of
     their rows would hang or average unlike things.  `signature`: a flat list of at most SIGNATURE_LEN numbers (Environment: per learner
-    its brain index, kind, entry point, exploration and soft_update_freq -- a wide DQN learner also its batch --, then learn_every, the learn_steps per kind and rollout_steps).
+    its brain index, kind, entry point, exploration and soft_update_freq -- a wide DQN or wide D3QN learner also its batch --, then learn_every, the learn_steps per kind and rollout_steps).
     `device`: where the row is made -- the worlds' device under nccl (= RCCL), whose process group serves device tensors only, as the
     Tracker makes its layout row; under gloo gather_rows takes a device row through the host.  ONE all-gather of a
     fixed-length row [length, numbers..., zero padding]; a mismatch raises the same ValueError on EVERY rank, with the table in the

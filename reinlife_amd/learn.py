@@ -1,4 +1,4 @@
-"""DeviceLearner: what a DQN (also on wide minibatches: wide_batch=, rl_learn_wide), D3QN, (prioritized=True) PERD3QN, (rollout=True) PPO or (td_priority=True) PERDQN brain needs to learn on
+"""DeviceLearner: what a DQN (also on wide minibatches: wide_batch=, rl_learn_wide), D3QN (also on wide minibatches: dueling_batch=, rl_learn_dueling_wide), (prioritized=True) PERD3QN, (rollout=True) PPO or (td_priority=True) PERDQN brain needs to learn on
 the device (rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo / rl_learn_td, include/reinlife_hip.h) -- the flat f32 master parameters,
 the target network, Adam's moments, the step / call counters and the packed weights the acting kernels read, all as device tensors.
 
@@ -62,9 +62,18 @@ def entry_of(kind):
 
 
 class DeviceLearner:
-    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False, td_priority=False, wide_batch=None):
+    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False, td_priority=False, wide_batch=None, dueling_batch=None):
         lib = _lib.lib()
-        if wide_batch is not None:   # an explicit opt-in, like the three below: entry_of() and ENTRY_BY_METHOD keep answering what they answered
+        if dueling_batch is not None:   # an explicit opt-in, like the four below: entry_of() and ENTRY_BY_METHOD keep answering what they answered
+            other = (" with wide_batch" if wide_batch is not None else " with prioritized=True" if prioritized else " with rollout=True" if rollout
+                     else " with td_priority=True" if td_priority else "")
+            if other or not lib.rl_learn_dueling_wide_supported(brain.kind):
+                raise ValueError("dueling_batch is for D3QN brains (rl_learn_dueling_wide); got a %s brain (kind %d)%s" % (brain.method, brain.kind, other))
+            if isinstance(dueling_batch, bool) or not isinstance(dueling_batch, (int, np.integer)) or not 1 <= dueling_batch <= _lib.LEARN_DUELING_WIDE_MAX:
+                raise ValueError("dueling_batch must be an int in [1, %d] (the rows of a minibatch of rl_learn_dueling_wide), got %r"
+                                 % (_lib.LEARN_DUELING_WIDE_MAX, dueling_batch))
+            self.entry = "rl_learn_dueling_wide"
+        elif wide_batch is not None:   # an explicit opt-in, like the three below: entry_of() and ENTRY_BY_METHOD keep answering what they answered
             other = " with prioritized=True" if prioritized else " with rollout=True" if rollout else " with td_priority=True" if td_priority else ""
             if other or not lib.rl_learn_wide_supported(brain.kind):
                 raise ValueError("wide_batch is for DQN brains (rl_learn_wide); got a %s brain (kind %d)%s" % (brain.method, brain.kind, other))
@@ -125,6 +134,8 @@ class DeviceLearner:
             self.gamma, self.batch = float(getattr(brain, "gamma", 0.99)), int(getattr(brain, "batch_size", 64))
             # random.sample needs `batch` rows (D3QN.py:98, 140): the only gate; np.random.choice (PERD3QN.py:165) needs one
             self.min_size = 0 if prioritized else self.batch - 1
+            if dueling_batch is not None:   # the wide learner is the D3QN learner with its own batch: the gate stays the brain's (rows are drawn with replacement)
+                self.batch = int(dueling_batch)
             self.exploration, self.soft_update_freq = int(getattr(brain, "exploration", 1000)), int(getattr(brain, "soft_update_freq", 200))
             self.n_steps_default = 1                             # D3QNAgent.train() makes one update
             self.sync_target = False                             # the schedule's (D3QN.py:125-126, Environment.learn_now)
@@ -147,6 +158,8 @@ class DeviceLearner:
         self.work = None          # wide_batch: rl_learn_wide's scratch (header, the tiles' partial gradients and loss sums); needs no initialisation
         if self.entry == "rl_learn_wide":
             self.work = torch.empty(int(lib.rl_learn_wide_work_bytes(self.kind, self.batch)), dtype=torch.uint8, device=self.device)
+        if self.entry == "rl_learn_dueling_wide":   # dueling_batch: rl_learn_dueling_wide's scratch (header, partial gradients, advantage sums, per-row stash)
+            self.work = torch.empty(int(lib.rl_learn_dueling_wide_work_bytes(self.kind, self.batch)), dtype=torch.uint8, device=self.device)
         self.rank_order = self.rank_work = None   # DeviceWorlds.draw_slots_rank: the ring's slots in key order, and rl_learn_draw_rank's scratch
         self.loss = None          # optional device float32 [n_steps]
         self.grad = None          # optional device float32 [n_steps, n_params] (tests, diagnostics)
@@ -248,7 +261,7 @@ class DeviceLearner:
             self._load(self.brain.model, self.params.cpu().numpy())
             self._load(self.brain.target_model, self.target.cpu().numpy())
             return
-        if self.entry in ("rl_learn_dueling", "rl_learn_prioritized"):
+        if self.entry in ("rl_learn_dueling", "rl_learn_prioritized", "rl_learn_dueling_wide"):
             self._load(self.brain.eval_net, self.params.cpu().numpy())
             self._load(self.brain.target_net, self.target.cpu().numpy())
             return

@@ -552,7 +552,10 @@ class DeviceWorlds:
         draw_rollout(), or the caller's own rows with gate=False, which leaves the empty-window gate out), a list of PERDQN learners to
         rl_learn_td (PERDQNAgent.train_model(): the loss scaled by the mean importance weight, the batch rows' priorities rewritten;
         `slots` from draw_td()), a list of wide DQN learners (DeviceLearner(..., wide_batch=B)) to rl_learn_wide (the DQN update on
-        minibatches of B <= 2048 rows, 32-row tiles side by side, 2 n_steps + 3 launches; `slots` from draw_slots() or None).  The
+        minibatches of B <= 2048 rows, 32-row tiles side by side, 2 n_steps + 3 launches; `slots` from draw_slots() or None), a list of
+        wide D3QN learners (DeviceLearner(..., dueling_batch=B)) to rl_learn_dueling_wide (the D3QN update on minibatches of B <= 2048
+        rows, 64-row tiles side by side with the advantage mean of the whole batch, 3 n_steps + 3 launches; one batch per call; `slots`
+        from draw_slots() / draw_slots_rank() or None).  The
         learners of one call must all belong to one entry point: ValueError otherwise."""
         if not learners:
             return
@@ -584,6 +587,12 @@ class DeviceWorlds:
             work = (C.c_void_p * n)(*[l.work.data_ptr() for l in learners])
             _lib.check(self.lib.rl_learn_wide(self.handle, arr, rings, n, int(n_steps), _ptr(slots), work, self._stream()), entry)
             self.launches += 2 * int(n_steps) + 2   # (2 n_steps + 3 in all: check, tiles and update per step, target / counters, pack)
+        elif entry == "rl_learn_dueling_wide":
+            if len({l.batch for l in learners}) != 1:
+                raise ValueError("learn(): the rl_learn_dueling_wide learners of a call must share one batch size, got %s" % sorted({l.batch for l in learners}))
+            work = (C.c_void_p * n)(*[l.work.data_ptr() for l in learners])
+            _lib.check(self.lib.rl_learn_dueling_wide(self.handle, arr, rings, n, int(n_steps), _ptr(slots), work, self._stream()), entry)
+            self.launches += 3 * int(n_steps) + 2   # (3 n_steps + 3 in all: check, the two tile passes and the update per step, target / counters, pack)
         else:
             _lib.check(getattr(self.lib, entry)(self.handle, arr, rings, n, int(n_steps), _ptr(slots), self._stream()), entry)
         self._learn_keep = slots   # (the launch reads the table asynchronously)
