@@ -272,6 +272,51 @@ struct TileIO {
 #endif
 };
 
+// The descriptor of k_run's certified one-wave tile: WAVE-UNIFORM values only, so it lives in SGPRs.  Everything per lane
+// is a function of the tile row's 16-bit list entry e (k = e & 0x7fff: row w * cap + k, Philox index k, action slot k, mirror row k; e &
+// 0x8000: padding), which the tile reads where it needs it, with a lane index taken there (tile_ref_row) -- a TileIO's per-lane fields
+// lived from above the tile to its last store, through 240 MFMAs of a kernel at the register limit, i.e. in scratch.
+struct TileRef {
+    gfloat* packed;
+    const float* obs;
+    int64_t row0;          // observation row of the world's list entry 0
+    int trow_lds_off;      // byte offset of the tile's 32 list entries (shorts) in the DYNAMIC LDS region
+    float eps;
+    int8_t* actions;       // [row], not null
+    uint64_t seed;
+    uint32_t key_world, key_tick, key_epoch;
+    int lds_actions_off;   // byte offset of the world's action array in the dynamic LDS region
+    int x_lds_off;         // byte offset of row 0 of the LDS mirror (rows of x_stride floats; rows k < xrows are mirrored), or -1
+    int x_stride, xrows;
+    int c_lds_off;         // as TileIO's
+#ifdef RL_PHASE_PROFILE
+    long long* prof;
+#endif
+};
+template <typename IO> struct is_tile_ref { static constexpr bool value = false; };
+template <> struct is_tile_ref<TileRef> { static constexpr bool value = true; };
+// A lane index that is nobody's loop invariant and nobody's common subexpression (rl_world_dev.h rl_lane_fresh, for the tiles)
+__device__ inline int tile_lane_fresh()
+{
+    int l = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+#endif
+    return l;
+}
+struct TileRow { int k; bool valid; };
+__device__ inline TileRow tile_ref_row(const TileRef& r, int lane)
+{
+    extern __shared__ __attribute__((aligned(16))) char rl_dyn_lds[];
+    const int e = *(const unsigned short*)(rl_dyn_lds + r.trow_lds_off + 2 * (lane & 31));
+    return TileRow{e & 0x7fff, !(e & 0x8000)};
+}
+// __shfl_xor(x, 32) of a TileRef tile, through the lane index it is given (__shfl_xor's own is a loop invariant of k_run's tick loop, spilled)
+__device__ inline float tile_swap32(float x, int lane)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, __builtin_bit_cast(int, x)));
+}
+
 #ifdef RL_PHASE_PROFILE
 #define RL_PMARK(i) do { if (io.prof && threadIdx.x == 0) io.prof[100 + (i)] = (long long)clock64(); } while (0)
 #else
@@ -838,16 +883,30 @@ __device__ __attribute__((noinline, cold)) void tile1_cert_fallback(TileIO io, c
 }
 // The finish without V: vbar >= |v| of the lane's row (see above); fallback(): what runs the value branch after all and finishes the tile
 // (the pair tile: tile1_cert_fallback on role 0; the one-wave tile: the whole full tile again, tile1s_full_cold).
-template <int KIND, typename Fallback>
-__device__ inline void tile1_finish_cert(const TileIO& io, int lane, const float (&adv)[4], const rl_u4& draw, const float* hconsts, float vbar,
+// A TileRef tile (k_run's one-wave tile) forms row, validity and action slot HERE, behind the last MFMA, from the list entry and a lane
+// index of its own, and its fallback() only reports (the caller runs the full tile from a descriptor it builds then).
+template <int KIND, typename IO, typename Fallback>
+__device__ inline void tile1_finish_cert(const IO& io, int lane, const float (&adv)[4], const rl_u4& draw, const float* hconsts, float vbar,
                                          Fallback&& fallback)
 {
+    constexpr bool kRef = is_tile_ref<IO>::value;
+    bool valid;
+    int64_t row;
+    int lds_slot;
+    if constexpr (kRef) {
+        lane = tile_lane_fresh();
+        const TileRow tr = tile_ref_row(io, lane);
+        valid = tr.valid; row = io.row0 + tr.k; lds_slot = tr.k;
+    } else { valid = io.valid; row = io.row; lds_slot = io.lds_slot; }
     const int h = lane >> 5;
     const f32x4 ba = *(const f32x4*)(hconsts + 8 + 4 * h);
     const float a4[4] = {adv[0] + ba.x, adv[1] + ba.y, adv[2] + ba.z, adv[3] + ba.w};   // (tile1_finish's a_i)
     float o4[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) o4[r] = __shfl_xor(a4[r], 32);
+    for (int r = 0; r < 4; ++r) {
+        if constexpr (kRef) o4[r] = tile_swap32(a4[r], lane);
+        else o4[r] = __shfl_xor(a4[r], 32);
+    }
     int act = 0;
     bool greedy = false, ok = true;
     if (h == 0) {
@@ -861,12 +920,17 @@ __device__ inline void tile1_finish_cert(const TileIO& io, int lane, const float
             amax = fmaxf(amax, fabsf(a[i])); s += a[i];
         }
         // (+ 2^-80: a floor far above what a flushed denormal can move, and far below any gap that matters)
-        const float thr = 0x1p-20f * (((amax + amax) + vbar) + 0x1p-80f) + (s - s);
+        float thr;
+        if constexpr (kRef) {   // (the same value: as plain constants 2^-20 and 2^-80 were invariants of k_run's tick loop, kept in scratch and reloaded here)
+            float rel20 = 0x1p-20f, floor80 = 0x1p-80f;
+            asm volatile("" : "+v"(rel20), "+v"(floor80));
+            thr = rel20 * (((amax + amax) + vbar) + floor80) + (s - s);
+        } else thr = 0x1p-20f * (((amax + amax) + vbar) + 0x1p-80f) + (s - s);
 #pragma unroll
         for (int j = 0; j < 7; ++j) ok = ok && (j >= is || best - a[j] > thr);
         const bool explore = (float)rl_u24(draw.x) < io.eps;
         act = explore ? (int)(draw.y >> 29) : is;
-        greedy = io.valid && io.actions && !explore;
+        greedy = valid && io.actions && !explore;
     }
     const bool need = greedy && !ok;
     RL_CERT_COUNT(__ballot(greedy), __ballot(greedy && ok), __any(need));
@@ -874,11 +938,11 @@ __device__ inline void tile1_finish_cert(const TileIO& io, int lane, const float
         fallback();
         return;
     }
-    if (h == 0 && io.valid && io.actions) {
-        io.actions[io.row] = (int8_t)act;
+    if (h == 0 && valid && io.actions) {
+        io.actions[row] = (int8_t)act;
         if (io.lds_actions_off >= 0) {
             extern __shared__ __attribute__((aligned(16))) char rl_dyn_lds[];
-            ((signed char*)rl_dyn_lds)[io.lds_actions_off + io.lds_slot] = (signed char)act;
+            ((signed char*)rl_dyn_lds)[io.lds_actions_off + lds_slot] = (signed char)act;
         }
     }
 }
@@ -926,10 +990,16 @@ __device__ inline float f32_up(double d)
 template <int KIND, bool COHERENT, int XM>
 __device__ __attribute__((noinline, cold)) void tile1s_full_cold(TileIO io);
 
-template <int KIND, bool COHERENT, bool PAIR = false, int XM = 0, bool CERT = false>   // XM: what is known about the rows (in_chunk_class): 0 nothing, 1 RL_XF_SCALE, 2 + RL_XF_INT_HEALTH
-__device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, const PairLds* pair_lds = nullptr, Tile1Part* part = nullptr)
+// IO = TileRef (k_run's certified one-wave tile): the per-lane operands come from the tile row's list entry where they are used, and every
+// lane-derived value behind the prologue from a lane index taken there (tile_lane_fresh) -- nothing of the descriptor and nothing derived from the
+// caller's lane index is alive (in scratch) through the MFMA streams.  Returns true where a valid greedy row failed the certificate and
+// NOTHING was stored: the caller runs the full tile (tile1s_full_cold).  Every other tile returns false.
+template <int KIND, bool COHERENT, bool PAIR = false, int XM = 0, bool CERT = false, typename IO>   // XM: what is known about the rows (in_chunk_class): 0 nothing, 1 RL_XF_SCALE, 2 + RL_XF_INT_HEALTH
+__device__ inline bool policy_tile1s(const IO& io, int lane, int role = 0, const PairLds* pair_lds = nullptr, Tile1Part* part = nullptr)
 {
     static_assert(KIND == RL_D3QN || KIND == RL_PERD3QN, "one-wave tile: dueling kinds");
+    constexpr bool kRef = is_tile_ref<IO>::value;
+    static_assert(!kRef || (CERT && !PAIR), "TileRef: the certified one-wave tile");
     extern __shared__ __attribute__((aligned(16))) char rl_dyn_lds[];
     constexpr int D = 3;
     const int h = lane >> 5;
@@ -942,10 +1012,18 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
     w1.start(packed + L.l1 + (PAIR ? role * (2 * kPlanes * 64 * 4) : 0), lane);
     // ---- the lane's half of its observation row, chunk by chunk: x[row][16c + 8h + 0..7] (see policy_tile1)
     f32x4 X[kInChunks][2];
+    int64_t row;
+    int x_lds_off;
+    uint32_t key_index;
+    if constexpr (kRef) {
+        const TileRow tr = tile_ref_row(io, lane);
+        row = io.row0 + tr.k; key_index = (uint32_t)tr.k;
+        x_lds_off = (io.x_lds_off >= 0 && tr.k < io.xrows) ? io.x_lds_off + tr.k * io.x_stride * (int)sizeof(float) : -1;
+    } else { row = io.row; key_index = io.key_index; x_lds_off = io.x_lds_off; }
     {
-        const int64_t rbase = io.row * RL_OBS_DIM;
-        if (io.x_lds_off >= 0) {
-            const float* xr = (const float*)(rl_dyn_lds + io.x_lds_off);
+        const int64_t rbase = row * RL_OBS_DIM;
+        if (x_lds_off >= 0) {
+            const float* xr = (const float*)(rl_dyn_lds + x_lds_off);
 #pragma unroll
             for (int c = 0; c < kInChunks; ++c)
 #pragma unroll
@@ -967,7 +1045,7 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
             }
     }
     rl_u4 draw = {0u, 0u, 0u, 0u};
-    if ((!PAIR || role == 0) && io.actions && io.eps > 0.0f) draw = rl_philox4x32(io.seed, io.key_epoch, io.key_world, io.key_tick, RL_SITE_ACT, io.key_index);
+    if ((!PAIR || role == 0) && io.actions && io.eps > 0.0f) draw = rl_philox4x32(io.seed, io.key_epoch, io.key_world, io.key_tick, RL_SITE_ACT, key_index);
     if (h == 1) { X[kInChunks - 1][0] = f32x4{X[kInChunks - 1][0].w, 0.0f, 0.0f, 0.0f}; X[kInChunks - 1][1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
     // the row's scale: known without looking when the rows are the world kernels' own (RL_XF_SCALE, see in_chunk_class) -- else from the row's
     // largest magnitude: four independent chains of max3(m, |a|, |b|), 40 instructions (the compiler's tree over fabsf / fmaxf is 92, and
@@ -984,7 +1062,8 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
                 max3_abs(m4[(2 * c + q + 2) & 3], X[c][q].z, X[c][q].w);
             }
         float m = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
-        m = fmaxf(m, __shfl_xor(m, 32));
+        if constexpr (kRef) m = fmaxf(m, tile_swap32(m, lane));
+        else m = fmaxf(m, __shfl_xor(m, 32));
         row_scale(m, sc0, un0);
     }
     f32x4 B1[kInChunks][kPlanes];
@@ -1038,7 +1117,7 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
             pair_lds->ex[((4 * role + c) * kPlanes + 1) * 64 + lane] = lo;
         }
         lds_barrier();
-        if (CERT && role) { RL_PMARK1(9); return; }   // V is not computed (tile1_finish_cert): role 1 is done with the input layer
+        if (CERT && role) { RL_PMARK1(9); return false; }   // V is not computed (tile1_finish_cert): role 1 is done with the input layer
 #pragma unroll
         for (int c = 0; c < 8; ++c)
 #pragma unroll
@@ -1057,11 +1136,13 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
             if (slot >= 2 && slot < 34) ep.step(0, slot - 2, F[0], F[1], un0, mrow);
         });
         RL_PMARK1(3);
-        w2.start(packed + l2, lane);
+        if constexpr (kRef) w2.start(packed + l2, tile_lane_fresh());
+        else w2.start(packed + l2, lane);
         ep.fetch(2, 0);
 #pragma unroll
         for (int e = 0; e < 32; ++e) ep.step(2, e, F[2], F[3], un0, mrow);
-        mrow = fmaxf(mrow, __shfl_xor(mrow, 32));
+        if constexpr (kRef) mrow = fmaxf(mrow, tile_swap32(mrow, tile_lane_fresh()));
+        else mrow = fmaxf(mrow, __shfl_xor(mrow, 32));
         zrow = mrow;
         row_scale(mrow, sc1, un1);
         // relu(feature) feeds both branches (PERD3QN.py:200-201): B2 chunk 2t + c = registers 8c .. 8c+7 of tile t
@@ -1083,24 +1164,27 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
     });
     RL_PMARK1(5);
     WRing<1, 1, 1, D> wh;
-    wh.start(packed + hd, lane, 0);
+    [[maybe_unused]] int lane_h = 0;   // TileRef: the head's lane index
+    if constexpr (kRef) { lane_h = tile_lane_fresh(); wh.start(packed + hd, lane_h, 0); }
+    else wh.start(packed + hd, lane, 0);
     ep.fetch(2, 0);
 #pragma unroll
     for (int e = 0; e < 32; ++e) ep.step(2, e, A[2], A[3], un1, mrow);
-    mrow = fmaxf(mrow, __shfl_xor(mrow, 32));
+    if constexpr (kRef) mrow = fmaxf(mrow, tile_swap32(mrow, lane_h));
+    else mrow = fmaxf(mrow, __shfl_xor(mrow, 32));
     float sc2, un2;
     row_scale(mrow, sc2, un2);
     auto araw = [&](int c, int e) { return A[c >> 1][8 * (c & 1) + e]; };
     float adv[4], val[4];
     RL_PMARK1(6);
-    if (PAIR) {
+    if constexpr (PAIR) {
         head_stream<D>(wh, *(const f32x4*)(hconsts + ((PAIR && role) ? 16 : 0) + 4 * h), araw, sc2, un2, adv);
         if constexpr (CERT) {   // role 0 (role 1 left after the exchange): the action without V, or the value branch after all
             const float* const kc = hconsts + kTileConstFloats - 768;
             tile1_finish_cert<KIND>(io, lane, adv, draw, hconsts, __builtin_fmaf(kc[1], zrow, kc[0]),
                                     [&]() { tile1_cert_fallback<KIND>(io, pair_lds->ex, un1, f32x4{adv[0], adv[1], adv[2], adv[3]}, draw); });
             RL_PMARK1(9);
-            return;
+            return false;
         }
         if (role) { if (h == 0) pair_lds->val[lane] = adv[0] + hconsts[16 + 8]; }
         else {
@@ -1109,16 +1193,24 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
             part->draw = draw;
         }
         RL_PMARK1(9);
-        return;
+        return false;
     }
+    if constexpr (kRef) {   // the action without V -- or nothing stored and `true`: the caller runs the full tile
+        head_stream<D>(wh, *(const f32x4*)(hconsts + 4 * (lane_h >> 5)), araw, sc2, un2, adv);
+        const float* const kc = hconsts + kTileConstFloats - 768;
+        bool failed = false;
+        tile1_finish_cert<KIND>(io, lane, adv, draw, hconsts, __builtin_fmaf(kc[1], zrow, kc[0]), [&]() { failed = true; });
+        RL_PMARK1(9);
+        return failed;
+    } else {
     head_stream<D>(wh, *(const f32x4*)(hconsts + 4 * h), araw, sc2, un2, adv);
     if constexpr (CERT) {   // the action without V (tile1_finish_cert) -- or, for a tile with a greedy row that fails the test, the full tile
         const float* const kc = hconsts + kTileConstFloats - 768;
         tile1_finish_cert<KIND>(io, lane, adv, draw, hconsts, __builtin_fmaf(kc[1], zrow, kc[0]), [&]() { tile1s_full_cold<KIND, COHERENT, XM>(io); });
         RL_PMARK1(9);
-        return;
+        return false;
     }
-    WRingH<8, D> w3;   // (started before the head its twelve fragments are spilled and reloaded inside the value branch's MFMA stream)
+    WRingH<8, D> w3;  // (started before the head its twelve fragments are spilled and reloaded inside the value branch's MFMA stream)
     w3.start(packed + L.l2b, lane);
     RL_PMARK1(7);
     // ---- value branch
@@ -1139,6 +1231,8 @@ __device__ inline void policy_tile1s(const TileIO& io, int lane, int role = 0, c
     head_stream<D>(wh, *(const f32x4*)(hconsts + 16 + 4 * h), araw, sc2, un2, val);
     RL_PMARK1(9);
     tile1_finish<KIND>(io, lane, adv, val[0] + hconsts[16 + 8], draw, *(const f32x4*)(hconsts + 8 + 4 * h));
+    return false;
+    }   // (not a TileRef tile)
 }
 template <int KIND, bool COHERENT, int XM>
 __device__ __attribute__((noinline, cold)) void tile1s_full_cold(TileIO io)

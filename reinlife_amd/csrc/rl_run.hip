@@ -466,6 +466,24 @@ __device__ __forceinline__ void run_policy1(const KParams& p, Smem& s, PolSmem& 
         if (io.prof && lane == 0) { io.prof[100] = t_entry; io.prof[110] = (long long)clock64(); }
 #endif
     };
+    [[maybe_unused]] auto tile_ref = [&](int ti, TileRef& r) {   // the same tile as tile_io(ti, ...), without its per-lane fields
+        const int b = __builtin_amdgcn_readfirstlane(ps.tbrain[ti]);
+        r.packed = (gfloat*)((const float* const __attribute__((address_space(4)))*)ka->ra.packed)[b];
+        r.obs = obs_rows;
+        r.row0 = (int64_t)w * p.cap;
+        r.trow_lds_off = (int)((char*)(ps.trow + ti * 32) - smem_base);
+        r.eps = run_eps<TRAIN>(ka, b, p.n_brains, ps);
+        r.actions = *(int8_t* const __attribute__((address_space(4)))*)&ka->ra.actions;
+        r.seed = p.seed;
+        r.key_world = (uint32_t)(p.world_base + w); r.key_tick = (uint32_t)s.scal[S_TICK]; r.key_epoch = (uint32_t)s.scal[S_EPOCH];
+        r.lds_actions_off = (int)((char*)s.action - smem_base);
+        r.x_lds_off = mirrored ? (int)((char*)ps.xmirror - smem_base) : -1; r.x_stride = kXStride; r.xrows = ps.xrows;
+        r.c_lds_off = ps.cconst ? (int)((char*)(ps.cconst + run_const_floats<KIND>() * b) - smem_base) : -1;
+#ifdef RL_PHASE_PROFILE
+        r.prof = (p.prof && (int)blockIdx.x == p.prof_world && wave == 0) ? p.prof : nullptr;
+        if (r.prof && rl_lane_fresh() == 0) { r.prof[100] = t_entry; r.prof[110] = (long long)clock64(); }
+#endif
+    };
     if constexpr (T == 1024) {
         // FOUR waves per tile, all on one SIMD (waves t, t + 4, t + 8, t + 12): policy_quad.  More than four tiles (> 128 agents or an uneven
         // brain split): rounds of four, rows from memory (the exchange slices alias the mirror; recycle_world drained the rows: meta[5]).
@@ -522,10 +540,24 @@ __device__ __forceinline__ void run_policy1(const KParams& p, Smem& s, PolSmem& 
         // straight to the closing barrier.  T = 512 where no Q value is stored: the tile certifies its argmax instead of computing V
         //  -- up to four tiles sit on waves 0-3 = one per SIMD.
         for (int ti = wave; ti < ntiles; ti += T / 64) {
+            if constexpr (T == 512 && TRAIN != 2) {
+                if (cert) {
+                    // The certified tile takes a TileRef (wave-uniform: SGPRs) and a lane index from inside this loop, so that nothing per
+                    // lane is this loop's or the tick loop's invariant.  A tile with a greedy row that fails the certificate has stored
+                    // nothing: the full tile runs here, in the same iteration and before the closing barrier, from a TileIO built now.
+                    TileRef ref;
+                    tile_ref(ti, ref);
+                    if (__builtin_expect(policy_tile1s<KIND, RL_RUN_COHERENT, false, RL_XM_DUELING_KERNEL, true>(ref, rl_lane_fresh()), 0)) {
+                        TileIO io;
+                        tile_io(ti, io, rl_lane_fresh() & 31);
+                        tile1s_full_cold<KIND, RL_RUN_COHERENT, RL_XM_DUELING_KERNEL>(io);
+                    }
+                    continue;
+                }
+            }
             TileIO io;
             tile_io(ti, io, j);
-            if (T == 512 && cert) policy_tile1s<KIND, RL_RUN_COHERENT, false, RL_XM_DUELING_KERNEL, T == 512 && TRAIN != 2>(io, lane);
-            else if (T == 512) policy_tile1s<KIND, RL_RUN_COHERENT, false, RL_XM_DUELING_KERNEL>(io, lane);
+            if (T == 512) policy_tile1s<KIND, RL_RUN_COHERENT, false, RL_XM_DUELING_KERNEL>(io, lane);
             else policy_tile1<KIND, RL_RUN_COHERENT, true>(io, lane);
         }
 #ifdef RL_PHASE_PROFILE
