@@ -573,6 +573,61 @@ int rl_learn_prioritized_supported(int kind);
 int rl_learn_prioritized(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners, int n_steps,
                          const int32_t* slots, void* stream);
 
+/* ---- prioritised replay on wide minibatches (PERD3QN) ------------------------------------------------------------ */
+/* THIS BUILD'S OWN -- the reference trains one world on ONE minibatch of 64 per train() (PERD3QN.py:94-115).  rl_learn_prioritized_wide
+ * is rl_learn_prioritized on a minibatch of 1 .. RL_LEARN_PRIORITIZED_WIDE_MAX rows: rl_learn_dueling_wide's update (64-row tiles side by
+ * side, the advantage mean taken over the WHOLE minibatch) on an RL_PERD3QN learner, plus the prioritised memory's upkeep.  A call whose
+ * batch is at most 64 (one tile), given the same slots, leaves every buffer rl_learn_prioritized writes -- params, target, adam_m,
+ * adam_v, state, packed, loss, grad, priority[0 .. capacity) and *prio_max -- with rl_learn_prioritized's bits.  rl_learn_prioritized,
+ * rl_learn_prioritized_draw, rl_learn_dueling, rl_learn_dueling_wide and every *_supported answer are unchanged by it. */
+#define RL_LEARN_PRIORITIZED_WIDE_MAX 2048
+/* 1 for the brain kinds rl_learn_prioritized_wide trains (RL_PERD3QN), 0 for the others */
+int rl_learn_prioritized_wide_supported(int kind);
+/* The bytes of one learner's work buffer for a minibatch of `batch` rows: rl_learn_dueling_wide_work_bytes' formula (the layout is
+ * rl_learn_dueling_wide's: header | partial[T] | sumA'[T] sumA[T] | stash[T], T = ceil(batch / 64)).  0, with rl_last_error set, for a
+ * kind rl_learn_prioritized_wide does not train or a batch outside [1, RL_LEARN_PRIORITIZED_WIDE_MAX]. */
+size_t rl_learn_prioritized_wide_work_bytes(int kind, int batch);
+/* rl_learn_prioritized_draw for wide minibatches: the same two launches (prepare, pick) with the same arithmetic, batch in
+ * [1, RL_LEARN_PRIORITIZED_WIDE_MAX] and ONE batch for all learners of a call.  Draw d = s * batch + j keeps its salt -- words 0-1 of
+ * rl_philox(seed, 0, i, (uint32)state[1], RL_SITE_LEARN_PRIO, d) -- so with batch <= 64 and n_steps = 1 the table is
+ * rl_learn_prioritized_draw's, bit for bit, and so are weight, keys and *seen.  n_steps x batch workgroups per learner, each a pass over
+ * the ring's rows.
+ *   slots     device int32 [n_learners][n_steps][batch]
+ * Everything else -- the stamp of the rows appended since the last draw, kind RL_PERD3QN (anything else: RL_E_UNSUPPORTED naming the
+ * kind), the rings' columns (age included), every pointer of rl_prio set, alpha > 0, n_steps in [1,65536], the two deviations -- is as
+ * rl_learn_prioritized_draw states it. */
+int rl_learn_prioritized_wide_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners,
+                                   int n_steps, int32_t* slots, void* stream);
+/* PERD3QNAgent.train() (PERD3QN.py:94-115) on wide minibatches for n_learners brains, on the rl_learner / rl_replay / rl_prio structures
+ * of rl_learn_prioritized and the work buffers of rl_learn_dueling_wide.
+ *   update      rl_learn_dueling_wide's, launch for launch and instruction for instruction (the size gate, the range check of every slot
+ *               before a row is fetched, the two tile passes, the update, `afterwards`): at any batch the eight learner buffers end with
+ *               the bits rl_learn_dueling_wide leaves on an RL_D3QN learner with the same parameters, ring and slots.
+ *   priorities  in the second tile pass of every step, where td is formed for every row of the batch: the thread that handles batch row
+ *               i = 64 t + r of its OWN tile t writes priority[slot_i] = |max_a q'_target(s'_i) - q_eval(s_i)[a_i]| (PERD3QN.py:110-111:
+ *               the reference's expression, not the TD error), each q with the mean of the WHOLE minibatch's advantages, from this
+ *               step's pre-update parameters.  The value depends only on the row's contents, the parameters and the two batch-wide
+ *               means, which every tile forms identically, and a row's forward arithmetic does not depend on its place in a tile: a slot
+ *               drawn several times, in one tile or in several, is written with equal bits -- there is no winner rule.  Later steps of a
+ *               call overwrite earlier ones (stream order).  Rows of a tile beyond the batch carry no slot and write nothing.
+ *   afterwards  as rl_learn_dueling_wide, and, in a call that trained (size > min_size, no bad slot), *prio_max = max(priority[0 ..
+ *               size)), size = min(*ring.count, capacity) as read at entry.  A call below the size gate leaves priority and prio_max
+ *               alone (state[1] is counted and sync_target honoured as always).
+ *   bad slots   a slot outside [0, size): error-flag code 6 ([1] = learner, [2] = step, [3] = the value; the first in table order), and
+ *               NONE of that learner's buffers -- priority and prio_max included -- is written; the other learners train.
+ *   order       PRECONDITION as rl_learn_prioritized: rl_learn_prioritized_wide_draw has run on these rings since the last row was
+ *               appended (the `slots` of this call are its output).
+ * 3 n_steps + 3 launches, all queued on `stream` (the count and the grids of rl_learn_dueling_wide).  No host read-back, no cooperative
+ * launch, no workgroup waits for another, no allocation, no float atomics: the same buffers give the same bits in every run and
+ * whatever else is in the launch.
+ * Validated on the host before anything is launched: kind must be RL_PERD3QN (anything else: RL_E_UNSUPPORTED naming the kind);
+ * otherwise RL_E_INVALID naming the argument: null handle / learners / rings / prios / work, slots == NULL (the draw is
+ * rl_learn_prioritized_wide_draw's job), n_learners in [1, RL_MAX_CAPTURE_BRAINS], n_steps in [1,65536], batch in
+ * [1, RL_LEARN_PRIORITIZED_WIDE_MAX] and equal for all learners, rl_learn_prioritized's null-pointer and capacity checks,
+ * prios[i].priority / prio_max / seen not null and alpha > 0, a null work[i]. */
+int rl_learn_prioritized_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners,
+                              int n_steps, const int32_t* slots, void* const* work, void* stream);
+
 /* ---- on-policy learning (PPO) ------------------------------------------------------------------------------------ */
 #define RL_PPO_ROLLOUT_MAX 32
 /* What a learning PPO brain needs beside its rl_learner and its rl_replay ring (which must carry `prob`): the hyperparameters of

@@ -118,6 +118,13 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     three scalars per step, summed in tile order in double, the same bits in every run.  Schedule, gate (exploration, a ring of at least
     batch_size rows), learn_steps per kind, target sync rule, learning rate, learn_draw and learn_ranks are the D3QN learners'; a call is
     3 learn_steps["D3QN"] + 3 launches instead of one.  {"D3QN": 64} gives the learners that learn_kinds alone gives, bit for bit.
+    With learn_prioritized=True (and only then: without it the key stays unknown) the dict also takes "PERD3QN" (this build's own -- the
+    reference's minibatch is 64 rows, PERD3QN.py:49, 95): every PERD3QN learner trains through rl_learn_prioritized_wide, rl_learn_dueling_wide's
+    tiled update on a minibatch of B rows drawn by priority (rl_learn_prioritized_wide_draw: the prioritised draw at that width), with the
+    priority of every one of the B rows rewritten from the whole batch's means and the maximum kept for the rows appended next.  Schedule,
+    gate (exploration, one row), ONE update per call, target sync rule, learning rate and learn_ranks are the PERD3QN learners'; a call
+    is 2 + 6 launches instead of 2 + 1.  {"PERD3QN": 64} gives the learners that learn_prioritized=True alone gives, bit for bit,
+    priorities and prio_max included.
     learn_draw (default None: every run is launch for launch and bit for bit what it was; "rank" needs learn="device" and at least one
     brain of the learning kinds -- one that rl_learn, rl_learn_wide or rl_learn_dueling trains -- anything else is a ValueError before a
     device is touched): THIS BUILD'S OWN.  The DQN, wide DQN and D3QN learners' minibatches are then drawn by rl_learn_draw_rank instead of

@@ -209,20 +209,27 @@ class Environment:
         # (this build's own: the reference's minibatch is 32, DQN.py:16).  None: rl_learn, as always.  Checked before a device is touched.
         # A dict by kind, like learn_steps: {"DQN": B}, {"D3QN": B} or both -- "D3QN": every D3QN learner trains through rl_learn_dueling_wide
         # on minibatches of B rows in 64-row tiles, the advantage mean taken over the whole batch (the reference's minibatch is 64, D3QN.py:98).
-        self.learn_batch_of = {"DQN": None, "D3QN": None}
+        # With learn_prioritized=True the dict also takes "PERD3QN": every PERD3QN learner trains through rl_learn_prioritized_wide on
+        # minibatches of B rows (the prioritised draw at that width, the priorities of all B rows written); without it the key stays unknown.
+        self.learn_batch_of = {"DQN": None, "D3QN": None, "PERD3QN": None}
         if isinstance(learn_batch, dict):
             limits = {"DQN": _lib.LEARN_WIDE_MAX, "D3QN": _lib.LEARN_DUELING_WIDE_MAX}
+            wide_entry = {"DQN": "rl_learn_wide", "D3QN": "rl_learn_dueling_wide", "PERD3QN": "rl_learn_prioritized_wide"}
+            if self.learn_prioritized:
+                limits["PERD3QN"] = _lib.LEARN_PRIORITIZED_WIDE_MAX
             unknown = [k for k in learn_batch if k not in limits]
             if unknown or not learn_batch:
-                raise ValueError("learn_batch as a dict takes the keys 'DQN' (rl_learn_wide) and 'D3QN' (rl_learn_dueling_wide) and at least one of them, got %r"
-                                 % (learn_batch,))
+                raise ValueError("learn_batch as a dict takes the keys 'DQN' (rl_learn_wide) and 'D3QN' (rl_learn_dueling_wide)%s and at least one of them, got %r"
+                                 % (" and, with learn_prioritized=True, 'PERD3QN' (rl_learn_prioritized_wide)," if self.learn_prioritized else "", learn_batch))
             for k, v in learn_batch.items():
                 if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= limits[k]:
                     raise ValueError("learn_batch[%r] must be an int in [1, %d] (the rows of a %s minibatch, %s), got %r"
-                                     % (k, limits[k], k, "rl_learn_wide" if k == "DQN" else "rl_learn_dueling_wide", v))
+                                     % (k, limits[k], k, wide_entry[k], v))
             if learn != "device":
                 raise ValueError("learn_batch needs learn='device' (got learn=%r)" % (learn,))
             for k in learn_batch:
+                if k == "PERD3QN":   # (learn_prioritized=True has made sure of a Models.PERD3QN brain; learn_kinds does not name this kind)
+                    continue
                 if k not in self.learn_kinds or not any(getattr(b, "method", None) == k for b in brains):
                     raise ValueError("learn_batch names %s: it needs at least one Models.%s brain among the learning kinds %r (got %s)"
                                      % (k, k, self.learn_kinds, ", ".join(str(getattr(b, "method", b)) for b in brains)))
@@ -376,8 +383,9 @@ class Environment:
                 wide = ({"wide_batch": self.learn_batch_of["DQN"]} if self.learn_batch_of["DQN"] is not None and entries[k] == "rl_learn" else
                         {"dueling_batch": self.learn_batch_of["D3QN"]} if self.learn_batch_of["D3QN"] is not None and entries[k] == "rl_learn_dueling" else {})
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], **wide)
+            pwide = {"prioritized_batch": self.learn_batch_of["PERD3QN"]} if self.learn_batch_of["PERD3QN"] is not None else {}
             for k in prio:
-                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], prioritized=True)
+                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], prioritized=True, **pwide)
             for k in ppo:
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], rollout=True)
             for k in td:
@@ -388,7 +396,7 @@ class Environment:
             # the default period is the smallest train_freq of the learners a run has WITHOUT learn_prioritized, so that the keyword does
             # not move their schedule; the prioritised learners' own train_freq counts only where they are the only learners -- and
             # likewise learn_rollout and the PPO learners', and learn_td_priority and the PERDQN learners'
-            timed = ([l for l in self.learners.values() if l.entry not in ("rl_learn_prioritized", "rl_learn_ppo", "rl_learn_td")]
+            timed = ([l for l in self.learners.values() if l.entry not in ("rl_learn_prioritized", "rl_learn_prioritized_wide", "rl_learn_ppo", "rl_learn_td")]
                      or [l for l in self.learners.values() if l.entry not in ("rl_learn_ppo", "rl_learn_td")]
                      or [l for l in self.learners.values() if l.entry != "rl_learn_td"] or list(self.learners.values()))
             self.learn_every = int(learn_every) if learn_every is not None else min(l.train_freq for l in timed)
@@ -412,12 +420,13 @@ class Environment:
             return
         from ..distributed import broadcast_from_rank0, check_learner_signature
         ls = [self.learners[k] for k in sorted(self.learners)]
-        entries = ("rl_learn", "rl_learn_dueling", "rl_learn_prioritized", "rl_learn_ppo", "rl_learn_td", "rl_learn_wide", "rl_learn_dueling_wide")
+        entries = ("rl_learn", "rl_learn_dueling", "rl_learn_prioritized", "rl_learn_ppo", "rl_learn_td", "rl_learn_wide", "rl_learn_dueling_wide",
+                   "rl_learn_prioritized_wide")   # (new entries go to the END: the signatures of runs without them stay what they were)
         sig = [len(ls)]
         for k in sorted(self.learners):
             l = self.learners[k]   # (exploration and soft_update_freq decide whether a learner is called and when its target is synced)
             sig += [k, l.kind, entries.index(l.entry), getattr(l, "exploration", 0), getattr(l, "soft_update_freq", 0)]
-            if l.entry in ("rl_learn_wide", "rl_learn_dueling_wide"):   # (the other entry points' batches come from the brains' classes: the signatures of runs without learn_batch stay what they were)
+            if l.entry in ("rl_learn_wide", "rl_learn_dueling_wide", "rl_learn_prioritized_wide"):   # (the other entry points' batches come from the brains' classes: the signatures of runs without learn_batch stay what they were)
                 sig += [l.batch]
         sig += [self.learn_every, self.learn_steps_of["DQN"], self.learn_steps_of["D3QN"], self.learn_steps_of["PERDQN"], self.rollout_steps]
         check_learner_signature(sig, self.dist, device=self.worlds.device)
@@ -756,6 +765,13 @@ class Environment:
                         "exploration, target synced every soft_update_freq episodes, rows drawn with probability priority^0.6 / sum by content key "
                         "with replacement; rows appended between two calls get the priority maximum as of the earlier call)"
                         % (prio, sorted({self.learners[k].batch for k in prio}), self.learn_every))
+        pwide = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_prioritized_wide")
+        if pwide:
+            note.append("brains %s trained on the device (rl_learn_prioritized_wide: one minibatch update of batch %d (learn_batch) in 64-row tiles, the "
+                        "advantage mean taken over the whole batch and the priorities of all its rows rewritten, every %d episodes once past the "
+                        "brain's exploration, target synced every soft_update_freq episodes, rows drawn with probability priority^0.6 / sum by "
+                        "content key with replacement; rows appended between two calls get the priority maximum as of the earlier call)"
+                        % (pwide, self.learn_batch_of["PERD3QN"], self.learn_every))
         ppo = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_ppo")
         if ppo:
             note.append("brains %s trained on the device (rl_learn_ppo: %d rollout(s) of %s rows, %s Adam steps each, every %d episodes; the rows are "
@@ -770,7 +786,7 @@ class Environment:
                         "every new row gets the reference's one priority (0 + 0.01) ** 0.6; epsilon decays once per update)"
                         % (td, self.learn_steps_of["PERDQN"], sorted({self.learners[k].batch for k in td}), self.learn_every))
         if frozen:
-            note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if (duel or prio or ppo or td) else
+            note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if (duel or prio or pwide or ppo or td) else
                         "brains %s as loaded / initialised (their kinds do not learn in this build)" % frozen)
         if self.learn_draw == "rank" and (wide or dqn or duel or dwide):
             note.append("the minibatches of brains %s drawn by content-key rank (learn_draw='rank', rl_learn_draw_rank: the ring's rows sorted by "
@@ -807,6 +823,11 @@ class Environment:
         learn_batch={"D3QN": B}: the D3QN learners are wide ones (rl_learn_dueling_wide, minibatches of B rows in 64-row tiles side by side,
         the advantage mean of the whole batch) and are called in the D3QN learners' place, the same way -- schedule, gate, draw, target
         rule --, 3 learn_steps["D3QN"] + 3 launches instead of one; B = 64 trains on rl_learn_dueling's rows and ends with its bits.
+        learn_batch={"PERD3QN": B} (with learn_prioritized=True): the PERD3QN learners are wide ones (rl_learn_prioritized_wide, minibatches
+        of B rows in 64-row tiles, the priorities of all B rows rewritten and their maximum kept) and are called in the PERD3QN learners'
+        place, the same way -- gate, target rule, ONE step, draw (rl_learn_prioritized_wide_draw, two launches) then learn (6 launches
+        instead of one) --, behind the DQN and D3QN calls; B = 64 draws rl_learn_prioritized's rows and ends with its bits, priorities and
+        prio_max included.
         learn_draw="rank": the draw_slots calls above -- the DQN, wide DQN and D3QN learners' -- are draw_slots_rank calls (rl_learn_draw_rank,
         six launches instead of two: the rings' rows sorted by content key once, every draw an index into that order); the prioritised,
         rollout and PERDQN draws are what they are.
@@ -831,7 +852,7 @@ class Environment:
                     l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
             self.worlds.learn(ls, n, slots=draw_slots(ls, n))
             called += ls
-        prio =[self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_prioritized"
+        prio =[self.learners[k] for k in sorted(self.learners) if self.learners[k].entry in ("rl_learn_prioritized", "rl_learn_prioritized_wide")   # (learn_batch naming PERD3QN: all wide)
                 and (last is None or last > self.learners[k].exploration)]
         for batch in sorted({l.batch for l in prio}):
             ls = [l for l in prio if l.batch == batch]

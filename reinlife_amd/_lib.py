@@ -91,6 +91,7 @@ MAX_CAPTURE_BRAINS = 16  # RL_MAX_CAPTURE_BRAINS
 MAX_MERGE_RANKS = 64     # rl_learn_merge: n_ranks at most
 LEARN_WIDE_MAX = 2048    # RL_LEARN_WIDE_MAX: the rows of a minibatch at most (rl_learn_wide)
 LEARN_DUELING_WIDE_MAX = 2048   # RL_LEARN_DUELING_WIDE_MAX: the rows of a minibatch at most (rl_learn_dueling_wide)
+LEARN_PRIORITIZED_WIDE_MAX = 2048   # RL_LEARN_PRIORITIZED_WIDE_MAX: the rows of a minibatch at most (rl_learn_prioritized_wide)
 LEARN_DRAW_RANK_LAUNCHES = 6   # RL_LEARN_DRAW_RANK_LAUNCHES: the launches of one rl_learn_draw_rank call
 PPO_ROLLOUT_MAX = 32    # RL_PPO_ROLLOUT_MAX: the rows of a rollout at most (rl_learn_ppo)
 
@@ -146,6 +147,10 @@ ABI = [
     ("rl_learn_prioritized_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Prio), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_prioritized_supported", C.c_int, [C.c_int]),
     ("rl_learn_prioritized", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Prio), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_prioritized_wide_supported", C.c_int, [C.c_int]),
+    ("rl_learn_prioritized_wide_work_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("rl_learn_prioritized_wide_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Prio), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_prioritized_wide", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Prio), C.c_int, C.c_int, _P, C.POINTER(_P), _P]),
     ("rl_learn_ppo_supported", C.c_int, [C.c_int]),
     ("rl_learn_ppo", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Ppo), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_rollout", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Ppo), C.c_int, C.c_int, _P, _P]),

@@ -35,6 +35,12 @@
 //                     every double sum above is the round trip float -> double -> float of one number: batch <= 64 is rl_learn_dueling.
 //   k_dwide_finish    once: target <- params where sync_target is set (also below the gate); state[0] += steps made, state[1] += 1.
 //   packing           rl_learn_merge.hip's k_pack_device, skipping a learner marked bad.
+//
+// Prioritised memory (rl_learn_prioritized_wide, RL_PERD3QN).  PERD3QNAgent.train() (PERD3QN.py:94-115) is D3QNAgent.train() plus
+// update_priorities(indices, |max_a q'_target(s') - q_eval(s)[a]|) (PERD3QN.py:110-111).  k_dwide_backward<true> and k_dwide_finish<true>
+// add exactly that to the <false> instantiations (which compile to what they were): the backward pass already forms the two numbers for
+// every row of the batch; the finish pass leaves max(priority[0 .. size)) in *prio_max.  The launches, their grids and the work buffer
+// are the same.
 #include "rl_learn_dev.h"
 
 int rl_learn_wide_pack_launch(const rl_learner*, int, const long long* const*, hipStream_t);   // rl_learn_merge.hip
@@ -79,6 +85,11 @@ struct DWideBrain {
     int min_size, sync_target;
 };
 
+struct DWidePrio {               // the prioritised memory of a brain (the <true> instantiations only: rl_learn_prioritized_wide)
+    float* priority;             // [ring capacity]
+    float* prio_max;             // [1]
+};
+
 struct DWideArgs {
     DWideBrain b[RL_MAX_CAPTURE_BRAINS];
     const int32_t* slots;        // [n_learners][n_steps][batch] or null
@@ -86,6 +97,7 @@ struct DWideArgs {
     uint64_t seed;
     int n_steps, batch, tiles;
     int step;                    // the per-step kernels: the step of this launch
+    DWidePrio p[RL_MAX_CAPTURE_BRAINS];   // (behind everything else: the fields above sit where they sat)
 };
 
 __host__ __device__ inline size_t dwide_sums_bytes(int tiles) { return ((size_t)2 * tiles * sizeof(float) + 15) & ~(size_t)15; }
@@ -391,6 +403,13 @@ __global__ __launch_bounds__(kDBlock) void k_dwide_forward(const DWideArgs A)
     }
 }
 
+// PRIO: the prioritised memory's upkeep (rl_learn_prioritized_wide), as k_learn_d3qn<true> adds it to k_learn_d3qn<false>.  In the all-rows
+// loop the thread that handles batch row i = 64 t + r of THIS tile (t == tile, i < batch) writes priority[row_slot[r]] = |mx - q|
+// (PERD3QN.py:110-111), from this step's pre-update parameters.  mx and q come from the row's stash entries and from M' and M, which every
+// tile forms identically; the forward arithmetic of a row is k ascending whatever its place in a tile: a slot drawn several times, in one
+// tile or in several, is written with equal bits, so no winner rule exists.  Padding rows (row_slot = -1) are not in the batch and never
+// index priority; k_dwide_check has range-checked every other slot against size <= capacity before this kernel runs.
+template <bool PRIO>
 __global__ __launch_bounds__(kDBlock) void k_dwide_backward(const DWideArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) float dwide_lds[];
@@ -446,6 +465,7 @@ __global__ __launch_bounds__(kDBlock) void k_dwide_backward(const DWideArgs A)
         const float g = in ? (2.0f * td) * inv_batch : 0.0f;
         all_l[t * (kDRows + 1) + r] = l;
         all_g[t * (kDRows + 1) + r] = g;
+        if (PRIO && t == tile && in) A.p[brain].priority[row_slot[r]] = fabsf(mx - q);   // only a row's own tile writes it
         if (t == tile) { row_g[r] = g; row_a[r] = ((const int*)st)[oSAct + r]; }
     }
     __syncthreads();
@@ -576,6 +596,9 @@ __global__ __launch_bounds__(kApplyBlock) void k_dwide_apply(const DWideArgs A)
     adam_update(ad, e, (float)sum);
 }
 
+// PRIO: block 0 of a learner leaves max(priority[0 .. size)) in *prio_max after a call that trained (a call below the size gate wrote no
+// priority and leaves the maximum alone, and so does a learner marked bad: it has returned above).  fmaxf is exact: the order is free.
+template <bool PRIO>
 __global__ __launch_bounds__(kApplyBlock) void k_dwide_finish(const DWideArgs A)
 {
     const int tid = threadIdx.x;
@@ -588,6 +611,21 @@ __global__ __launch_bounds__(kApplyBlock) void k_dwide_finish(const DWideArgs A)
     }
     const int e = blockIdx.x * kApplyBlock + tid;
     if (B.sync_target && e < kNParams) B.target[e] = B.params[e];   // D3QN.py:125-126, on the caller's schedule, also below the size gate
+    if constexpr (PRIO) {
+        __shared__ float prio_red[kApplyBlock];
+        const long long size = hdr[kHdrSize];
+        if (blockIdx.x != 0 || !hdr[kHdrTrain] || size <= 0) return;   // (uniform)
+        const float* pr = A.p[blockIdx.y].priority;
+        float mx = 0.0f;      // (priorities are |.|: never below zero)
+        for (long long i = tid; i < size; i += kApplyBlock) mx = fmaxf(mx, pr[i]);
+        prio_red[tid] = mx;
+        __syncthreads();
+        for (int o = kApplyBlock / 2; o > 0; o >>= 1) {
+            if (tid < o) prio_red[tid] = fmaxf(prio_red[tid], prio_red[tid + o]);
+            __syncthreads();
+        }
+        if (tid == 0) *A.p[blockIdx.y].prio_max = prio_red[0];
+    }
 }
 
 }  // namespace
@@ -600,8 +638,9 @@ size_t rl_learn_dueling_wide_work_bytes_impl(int batch)
     return kHdrBytes + tiles * kNParams * sizeof(float) + dwide_sums_bytes((int)tiles) + tiles * kStashFloats * sizeof(float);
 }
 
-int rl_learn_dueling_wide_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps,
-                                 const int32_t* slots, void* const* work, hipStream_t stream)
+template <bool PRIO>
+static int dwide_launch(const char* who, rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners,
+                        int n_steps, const int32_t* slots, void* const* work, hipStream_t stream)
 {
     DWideArgs a{};
     const long long* bad[RL_MAX_CAPTURE_BRAINS];
@@ -617,25 +656,42 @@ int rl_learn_dueling_wide_launch(rl_world* h, const rl_learner* learners, const 
         b.lr = learn_decimal(l.lr); b.beta1 = learn_decimal(l.beta1); b.beta2 = learn_decimal(l.beta2);
         b.gamma = l.gamma; b.eps_d = learn_decimal(l.eps);
         b.min_size = l.min_size; b.sync_target = l.sync_target;
+        if (PRIO) { a.p[i].priority = prios[i].priority; a.p[i].prio_max = prios[i].prio_max; }
         bad[i] = (const long long*)work[i] + kHdrBad;
     }
     a.slots = slots; a.err = h->err_flag; a.seed = h->cfg.seed; a.n_steps = n_steps;
     a.batch = learners[0].batch; a.tiles = (a.batch + kDRows - 1) / kDRows;
     {   // the large dynamic-LDS window (158 KB), per kernel: asked for at every call -- idempotent, host-only, and right on whatever device is current
         hipError_t e = hipFuncSetAttribute((const void*)k_dwide_forward, hipFuncAttributeMaxDynamicSharedMemorySize, kDLdsBytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_dwide_backward, hipFuncAttributeMaxDynamicSharedMemorySize, kDLdsBytes);
-        if (e != hipSuccess) { rl_set_error("rl_learn_dueling_wide: hipFuncSetAttribute(%d bytes of LDS) failed: %s", kDLdsBytes, hipGetErrorString(e)); return RL_E_LAUNCH; }
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_dwide_backward<PRIO>, hipFuncAttributeMaxDynamicSharedMemorySize, kDLdsBytes);
+        if (e != hipSuccess) { rl_set_error("%s: hipFuncSetAttribute(%d bytes of LDS) failed: %s", who, kDLdsBytes, hipGetErrorString(e)); return RL_E_LAUNCH; }
     }
     const int pblocks = (kNParams + kApplyBlock - 1) / kApplyBlock;
     hipLaunchKernelGGL(k_dwide_check, dim3(n_learners), dim3(kApplyBlock), 0, stream, a);
     for (int s = 0; s < n_steps; ++s) {
         a.step = s;
         hipLaunchKernelGGL(k_dwide_forward, dim3(a.tiles, n_learners), dim3(kDBlock), kDLdsBytes, stream, a);
-        hipLaunchKernelGGL(k_dwide_backward, dim3(a.tiles, n_learners), dim3(kDBlock), kDLdsBytes, stream, a);
+        hipLaunchKernelGGL(k_dwide_backward<PRIO>, dim3(a.tiles, n_learners), dim3(kDBlock), kDLdsBytes, stream, a);
         hipLaunchKernelGGL(k_dwide_apply, dim3(pblocks, n_learners), dim3(kApplyBlock), 0, stream, a);
     }
-    hipLaunchKernelGGL(k_dwide_finish, dim3(pblocks, n_learners), dim3(kApplyBlock), 0, stream, a);
+    hipLaunchKernelGGL(k_dwide_finish<PRIO>, dim3(pblocks, n_learners), dim3(kApplyBlock), 0, stream, a);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rl_set_error("rl_learn_dueling_wide: kernel launch failed: %s", hipGetErrorString(e)); return RL_E_LAUNCH; }
+    if (e != hipSuccess) { rl_set_error("%s: kernel launch failed: %s", who, hipGetErrorString(e)); return RL_E_LAUNCH; }
     return rl_learn_wide_pack_launch(learners, n_learners, bad, stream);
+}
+
+int rl_learn_dueling_wide_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, int n_learners, int n_steps,
+                                 const int32_t* slots, void* const* work, hipStream_t stream)
+{
+    return dwide_launch<false>("rl_learn_dueling_wide", h, learners, rings, nullptr, n_learners, n_steps, slots, work, stream);
+}
+
+// rl_learn_prioritized_wide: the same launches with the <true> instantiations of the backward and finish kernels; the work buffer is
+// rl_learn_dueling_wide's, byte for byte.
+int rl_learn_prioritized_wide_supported_impl(int kind) { return kind == RL_PERD3QN ? 1 : 0; }
+
+int rl_learn_prioritized_wide_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners,
+                                     int n_steps, const int32_t* slots, void* const* work, hipStream_t stream)
+{
+    return dwide_launch<true>("rl_learn_prioritized_wide", h, learners, rings, prios, n_learners, n_steps, slots, work, stream);
 }

@@ -164,6 +164,14 @@ int rl_learn_prioritized_draw_launch(rl_world* h, const rl_learner* learners, co
     return prio_draw_launch<false>("rl_learn_prioritized_draw", h, learners, rings, prios, nullptr, n_learners, n_steps, slots, stream);
 }
 
+// rl_learn_prioritized_wide_draw: the same two launches for batches up to RL_LEARN_PRIORITIZED_WIDE_MAX (the kernels are written over any
+// batch: one workgroup per draw d = s * batch + j, salted by d) -- at batch <= 64 rl_learn_prioritized_draw's table, bit for bit.
+int rl_learn_prioritized_wide_draw_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners,
+                                          int n_steps, int32_t* slots, hipStream_t stream)
+{
+    return prio_draw_launch<false>("rl_learn_prioritized_wide_draw", h, learners, rings, prios, nullptr, n_learners, n_steps, slots, stream);
+}
+
 int rl_learn_td_draw_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners,
                             int n_steps, int32_t* slots, hipStream_t stream)
 {

@@ -20,7 +20,9 @@ agent's learner (rl_learn_prioritized): besides the D3QN learner's tensors it ow
 maximum, the ring count as of the last draw, and two scratch columns of the draw (DeviceWorlds.draw_prioritized: probability
 priority^0.6 / sum, with replacement, by content key).  Its only size gate is np.random.choice's need of one row (min_size = 0).  The
 same two deviations apply, and one more follows from the first: every row appended between two learning calls gets the priority
-maximum as of the earlier call.
+maximum as of the earlier call.  DeviceLearner(brain, device, ring, prioritized=True, prioritized_batch=B) is the same learner on wide
+minibatches of B <= 2048 rows (rl_learn_prioritized_wide, this build's own: rl_learn_dueling_wide's tiled update with the priorities of
+all B rows written and their maximum kept); it also owns that entry point's work buffer.
 
 PPOAgent (ReinLife/Models/PPO.py:10-77) owns one module, `model`, with its own Adam (PPO.py:99) and the list of transitions gathered since
 the last learn() (PPO.py:88, 114-115); learn() (PPO.py:136-162) makes k_epoch full-batch Adam steps on that list and empties it.
@@ -62,9 +64,20 @@ def entry_of(kind):
 
 
 class DeviceLearner:
-    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False, td_priority=False, wide_batch=None, dueling_batch=None):
+    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False, td_priority=False, prioritized_batch=None, wide_batch=None, dueling_batch=None):
         lib = _lib.lib()
-        if dueling_batch is not None:   # an explicit opt-in, like the four below: entry_of() and ENTRY_BY_METHOD keep answering what they answered
+        if prioritized_batch is not None:   # an explicit opt-in on top of prioritized=True: the prioritised learner on wide minibatches
+            other = (" with wide_batch" if wide_batch is not None else " with dueling_batch" if dueling_batch is not None else " with rollout=True" if rollout
+                     else " with td_priority=True" if td_priority else "" if prioritized else " without prioritized=True")
+            if other or not lib.rl_learn_prioritized_wide_supported(brain.kind):
+                raise ValueError("prioritized_batch is for PERD3QN brains with prioritized=True (rl_learn_prioritized_wide); got a %s brain (kind %d)%s"
+                                 % (brain.method, brain.kind, other))
+            if (isinstance(prioritized_batch, bool) or not isinstance(prioritized_batch, (int, np.integer))
+                    or not 1 <= prioritized_batch <= _lib.LEARN_PRIORITIZED_WIDE_MAX):
+                raise ValueError("prioritized_batch must be an int in [1, %d] (the rows of a minibatch of rl_learn_prioritized_wide), got %r"
+                                 % (_lib.LEARN_PRIORITIZED_WIDE_MAX, prioritized_batch))
+            self.entry = "rl_learn_prioritized_wide"
+        elif dueling_batch is not None:   # an explicit opt-in, like the four below: entry_of() and ENTRY_BY_METHOD keep answering what they answered
             other = (" with wide_batch" if wide_batch is not None else " with prioritized=True" if prioritized else " with rollout=True" if rollout
                      else " with td_priority=True" if td_priority else "")
             if other or not lib.rl_learn_dueling_wide_supported(brain.kind):
@@ -136,6 +149,8 @@ class DeviceLearner:
             self.min_size = 0 if prioritized else self.batch - 1
             if dueling_batch is not None:   # the wide learner is the D3QN learner with its own batch: the gate stays the brain's (rows are drawn with replacement)
                 self.batch = int(dueling_batch)
+            if prioritized_batch is not None:   # likewise the prioritised learner: np.random.choice's gate (one row) stays
+                self.batch = int(prioritized_batch)
             self.exploration, self.soft_update_freq = int(getattr(brain, "exploration", 1000)), int(getattr(brain, "soft_update_freq", 200))
             self.n_steps_default = 1                             # D3QNAgent.train() makes one update
             self.sync_target = False                             # the schedule's (D3QN.py:125-126, Environment.learn_now)
@@ -160,6 +175,8 @@ class DeviceLearner:
             self.work = torch.empty(int(lib.rl_learn_wide_work_bytes(self.kind, self.batch)), dtype=torch.uint8, device=self.device)
         if self.entry == "rl_learn_dueling_wide":   # dueling_batch: rl_learn_dueling_wide's scratch (header, partial gradients, advantage sums, per-row stash)
             self.work = torch.empty(int(lib.rl_learn_dueling_wide_work_bytes(self.kind, self.batch)), dtype=torch.uint8, device=self.device)
+        if self.entry == "rl_learn_prioritized_wide":   # prioritized_batch: rl_learn_prioritized_wide's scratch (rl_learn_dueling_wide's layout)
+            self.work = torch.empty(int(lib.rl_learn_prioritized_wide_work_bytes(self.kind, self.batch)), dtype=torch.uint8, device=self.device)
         self.rank_order = self.rank_work = None   # DeviceWorlds.draw_slots_rank: the ring's slots in key order, and rl_learn_draw_rank's scratch
         self.loss = None          # optional device float32 [n_steps]
         self.grad = None          # optional device float32 [n_steps, n_params] (tests, diagnostics)
@@ -190,7 +207,7 @@ class DeviceLearner:
         self.seen = torch.zeros(1, dtype=torch.int64, device=self.device)
 
     def prio_struct(self):
-        if self.entry != "rl_learn_prioritized":
+        if self.entry not in ("rl_learn_prioritized", "rl_learn_prioritized_wide"):
             raise _lib.ReinLifeHipError("this DeviceLearner has no prioritised memory (DeviceLearner(..., prioritized=True))")
         if self.ring is None:
             raise _lib.ReinLifeHipError("this DeviceLearner has no replay ring (DeviceLearner.ring)")
@@ -261,7 +278,7 @@ class DeviceLearner:
             self._load(self.brain.model, self.params.cpu().numpy())
             self._load(self.brain.target_model, self.target.cpu().numpy())
             return
-        if self.entry in ("rl_learn_dueling", "rl_learn_prioritized", "rl_learn_dueling_wide"):
+        if self.entry in ("rl_learn_dueling", "rl_learn_prioritized", "rl_learn_dueling_wide", "rl_learn_prioritized_wide"):
             self._load(self.brain.eval_net, self.params.cpu().numpy())
             self._load(self.brain.target_net, self.target.cpu().numpy())
             return

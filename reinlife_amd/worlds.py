@@ -479,20 +479,26 @@ class DeviceWorlds:
         PrioritizedReplayBuffer.sample's draw (PERD3QN.py:157-165) on the device (rl_learn_prioritized_draw) -- first every row appended
         since the last draw gets the priority maximum (store(), PERD3QN.py:147-153), then each draw takes a row with probability
         priority^alpha / sum, with replacement, by a key of the rows' content: the same rows whatever slots they sit in.  All n_steps
-        are drawn from the priorities as they stand now.  Device int32 [len(learners), n_steps, batch], queued on the current stream."""
+        are drawn from the priorities as they stand now.  Device int32 [len(learners), n_steps, batch], queued on the current stream.
+        A list of wide prioritised learners (DeviceLearner(..., prioritized=True, prioritized_batch=B)) goes to
+        rl_learn_prioritized_wide_draw: the same two launches and the same arithmetic for batches up to 2048 (B <= 64 with n_steps = 1:
+        rl_learn_prioritized_draw's table).  The learners of a call are all of the one kind or all of the other."""
         n = len(learners)
         if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
             raise ValueError("draw_prioritized(): 1 to %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
         if len({l.batch for l in learners}) != 1:
             raise ValueError("draw_prioritized(): the learners of a call must share one batch size")
-        if any(l.entry != "rl_learn_prioritized" for l in learners):
+        if any(l.entry not in ("rl_learn_prioritized", "rl_learn_prioritized_wide") for l in learners):
             raise ValueError("draw_prioritized(): every learner must be a prioritised one (DeviceLearner(..., prioritized=True))")
+        entries = {l.entry for l in learners}
+        if len(entries) != 1:
+            raise ValueError("draw_prioritized(): the learners of a call must be of one kind (one entry point), got %s" % sorted(entries))
+        draw = "rl_learn_prioritized_draw" if entries == {"rl_learn_prioritized"} else "rl_learn_prioritized_wide_draw"
         arr = (_lib.Learner * n)(*[l.struct() for l in learners])
         rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
         prios = (_lib.Prio * n)(*[l.prio_struct() for l in learners])
         slots = torch.zeros((n, int(n_steps), int(learners[0].batch)), dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.rl_learn_prioritized_draw(self.handle, arr, rings, prios, n, int(n_steps), _ptr(slots), self._stream()),
-                   "rl_learn_prioritized_draw")
+        _lib.check(getattr(self.lib, draw)(self.handle, arr, rings, prios, n, int(n_steps), _ptr(slots), self._stream()), draw)
         self.launches += 2
         return slots
 
@@ -555,7 +561,9 @@ class DeviceWorlds:
         minibatches of B <= 2048 rows, 32-row tiles side by side, 2 n_steps + 3 launches; `slots` from draw_slots() or None), a list of
         wide D3QN learners (DeviceLearner(..., dueling_batch=B)) to rl_learn_dueling_wide (the D3QN update on minibatches of B <= 2048
         rows, 64-row tiles side by side with the advantage mean of the whole batch, 3 n_steps + 3 launches; one batch per call; `slots`
-        from draw_slots() / draw_slots_rank() or None).  The
+        from draw_slots() / draw_slots_rank() or None), a list of wide prioritised PERD3QN learners (DeviceLearner(..., prioritized=True,
+        prioritized_batch=B)) to rl_learn_prioritized_wide (that tiled update plus the priorities of all B rows and their maximum, 3 n_steps
+        + 3 launches; one batch per call; `slots` must come from draw_prioritized()).  The
         learners of one call must all belong to one entry point: ValueError otherwise."""
         if not learners:
             return
@@ -577,6 +585,13 @@ class DeviceWorlds:
         if entry == "rl_learn_prioritized":
             prios = (_lib.Prio * n)(*[l.prio_struct() for l in learners])
             _lib.check(self.lib.rl_learn_prioritized(self.handle, arr, rings, prios, n, int(n_steps), _ptr(slots), self._stream()), entry)
+        elif entry == "rl_learn_prioritized_wide":
+            if len({l.batch for l in learners}) != 1:
+                raise ValueError("learn(): the rl_learn_prioritized_wide learners of a call must share one batch size, got %s" % sorted({l.batch for l in learners}))
+            prios = (_lib.Prio * n)(*[l.prio_struct() for l in learners])
+            work = (C.c_void_p * n)(*[l.work.data_ptr() for l in learners])
+            _lib.check(self.lib.rl_learn_prioritized_wide(self.handle, arr, rings, prios, n, int(n_steps), _ptr(slots), work, self._stream()), entry)
+            self.launches += 3 * int(n_steps) + 2   # (3 n_steps + 3 in all, as rl_learn_dueling_wide)
         elif entry == "rl_learn_td":
             tds = (_lib.TdPrio * n)(*[l.td_struct() for l in learners])
             _lib.check(self.lib.rl_learn_td(self.handle, arr, rings, tds, n, int(n_steps), _ptr(slots), self._stream()), entry)
