@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..learn import BUFFER_LIMIT, ENTRIES, ENTRY, ENTRY_BY_METHOD, FAMILIES, DeviceLearner, entry_of
 from ..worlds import DeviceWorlds
 from .utils import Actions, EntityTypes
 
@@ -166,7 +167,6 @@ class Environment:
             raise ValueError("learn must be None (the brains stay as they are) or 'device' (DQN brains train through rl_learn), got %r" % (learn,))
         # learn_kinds: the brain methods that train under learn="device".  None = ("DQN",): what learn="device" always did; "D3QN" is an
         # explicit opt-in (rl_learn_dueling).  Checked here, before a device is touched.
-        from ..learn import ENTRY_BY_METHOD
         if learn_kinds is not None and learn != "device":
             raise ValueError("learn_kinds needs learn='device' (got learn=%r)" % (learn,))
         self.learn_kinds = ("DQN",) if learn_kinds is None else ((learn_kinds,) if isinstance(learn_kinds, str) else tuple(learn_kinds))
@@ -176,68 +176,49 @@ class Environment:
                              % (", ".join(map(str, unknown)) or "()", ", ".join(sorted(ENTRY_BY_METHOD))))
         # learn_prioritized=True: every PERD3QN brain trains through rl_learn_prioritized on a prioritised memory (PERD3QN.py:94-115,
         # 133-182).  A keyword of its own: learn_kinds and ENTRY_BY_METHOD answer what they answered.  Checked before a device is touched.
-        if learn_prioritized not in (None, True):
-            raise ValueError("learn_prioritized must be None or True, got %r" % (learn_prioritized,))
-        if learn_prioritized and learn != "device":
-            raise ValueError("learn_prioritized=True needs learn='device' (got learn=%r)" % (learn,))
-        if learn_prioritized and not any(getattr(b, "method", None) == "PERD3QN" for b in brains):
-            raise ValueError("learn_prioritized=True needs at least one Models.PERD3QN brain (got %s)" % ", ".join(str(getattr(b, "method", b)) for b in brains))
-        self.learn_prioritized = bool(learn_prioritized)
+        self._opt_in("prioritized", learn_prioritized, learn, brains)
         # learn_rollout=True: every PPO brain trains through rl_learn_ppo on rollouts drawn from the rows its current weights made
         # (PPO.py:71-77, 136-162).  A keyword of its own, like learn_prioritized.  Checked before a device is touched.
-        if learn_rollout not in (None, True):
-            raise ValueError("learn_rollout must be None or True, got %r" % (learn_rollout,))
-        if learn_rollout and learn != "device":
-            raise ValueError("learn_rollout=True needs learn='device' (got learn=%r)" % (learn,))
-        if learn_rollout and not any(getattr(b, "method", None) == "PPO" for b in brains):
-            raise ValueError("learn_rollout=True needs at least one Models.PPO brain (got %s)" % ", ".join(str(getattr(b, "method", b)) for b in brains))
+        self._opt_in("rollout", learn_rollout, learn, brains)
         if rollout_steps != 1 and not learn_rollout:
             raise ValueError("rollout_steps needs learn_rollout=True")
         if int(rollout_steps) < 1:
             raise ValueError("rollout_steps must be >= 1 (got %r)" % (rollout_steps,))
-        self.learn_rollout, self.rollout_steps = bool(learn_rollout), int(rollout_steps)
+        self.rollout_steps = int(rollout_steps)
         # learn_td_priority=True: every PERDQN brain trains through rl_learn_td on the reference's prioritised memory with importance
         # weights (PERDQN.py: train_model, Memory).  A keyword of its own, like learn_prioritized.  Checked before a device is touched.
-        if learn_td_priority not in (None, True):
-            raise ValueError("learn_td_priority must be None or True, got %r" % (learn_td_priority,))
-        if learn_td_priority and learn != "device":
-            raise ValueError("learn_td_priority=True needs learn='device' (got learn=%r)" % (learn,))
-        if learn_td_priority and not any(getattr(b, "method", None) == "PERDQN" for b in brains):
-            raise ValueError("learn_td_priority=True needs at least one Models.PERDQN brain (got %s)" % ", ".join(str(getattr(b, "method", b)) for b in brains))
-        self.learn_td_priority = bool(learn_td_priority)
+        self._opt_in("td_priority", learn_td_priority, learn, brains)
         # learn_batch=B: every DQN learner trains through rl_learn_wide on minibatches of B rows (1 .. 2048) in 32-row tiles side by side
         # (this build's own: the reference's minibatch is 32, DQN.py:16).  None: rl_learn, as always.  Checked before a device is touched.
         # A dict by kind, like learn_steps: {"DQN": B}, {"D3QN": B} or both -- "D3QN": every D3QN learner trains through rl_learn_dueling_wide
         # on minibatches of B rows in 64-row tiles, the advantage mean taken over the whole batch (the reference's minibatch is 64, D3QN.py:98).
         # With learn_prioritized=True the dict also takes "PERD3QN": every PERD3QN learner trains through rl_learn_prioritized_wide on
         # minibatches of B rows (the prioritised draw at that width, the priorities of all B rows written); without it the key stays unknown.
-        self.learn_batch_of = {"DQN": None, "D3QN": None, "PERD3QN": None}
+        wide = {e.method: e for e in ENTRIES if e.narrow}   # the wide entry per brain method, a key of the dict only where its narrow entry is on
+        self.learn_batch_of = dict.fromkeys(wide)
         if isinstance(learn_batch, dict):
-            limits = {"DQN": _lib.LEARN_WIDE_MAX, "D3QN": _lib.LEARN_DUELING_WIDE_MAX}
-            wide_entry = {"DQN": "rl_learn_wide", "D3QN": "rl_learn_dueling_wide", "PERD3QN": "rl_learn_prioritized_wide"}
-            if self.learn_prioritized:
-                limits["PERD3QN"] = _lib.LEARN_PRIORITIZED_WIDE_MAX
-            unknown = [k for k in learn_batch if k not in limits]
+            on = {k: e for k, e in wide.items() if not ENTRY[e.narrow].keyword or getattr(self, "learn_" + ENTRY[e.narrow].keyword)}
+            unknown = [k for k in learn_batch if k not in on]
             if unknown or not learn_batch:
                 raise ValueError("learn_batch as a dict takes the keys 'DQN' (rl_learn_wide) and 'D3QN' (rl_learn_dueling_wide)%s and at least one of them, got %r"
                                  % (" and, with learn_prioritized=True, 'PERD3QN' (rl_learn_prioritized_wide)," if self.learn_prioritized else "", learn_batch))
             for k, v in learn_batch.items():
-                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= limits[k]:
-                    raise ValueError("learn_batch[%r] must be an int in [1, %d] (the rows of a %s minibatch, %s), got %r"
-                                     % (k, limits[k], k, wide_entry[k], v))
+                limit = getattr(_lib, on[k].batch_max)
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= limit:
+                    raise ValueError("learn_batch[%r] must be an int in [1, %d] (the rows of a %s minibatch, %s), got %r" % (k, limit, k, on[k].name, v))
             if learn != "device":
                 raise ValueError("learn_batch needs learn='device' (got learn=%r)" % (learn,))
             for k in learn_batch:
-                if k == "PERD3QN":   # (learn_prioritized=True has made sure of a Models.PERD3QN brain; learn_kinds does not name this kind)
+                if ENTRY[on[k].narrow].keyword:   # (learn_prioritized=True has made sure of a Models.PERD3QN brain; learn_kinds does not name this kind)
                     continue
                 if k not in self.learn_kinds or not any(getattr(b, "method", None) == k for b in brains):
                     raise ValueError("learn_batch names %s: it needs at least one Models.%s brain among the learning kinds %r (got %s)"
                                      % (k, k, self.learn_kinds, ", ".join(str(getattr(b, "method", b)) for b in brains)))
             self.learn_batch_of.update({k: int(v) for k, v in learn_batch.items()})
-        elif learn_batch is not None:
-            if isinstance(learn_batch, bool) or not isinstance(learn_batch, (int, np.integer)) or not 1 <= learn_batch <= _lib.LEARN_WIDE_MAX:
-                raise ValueError("learn_batch must be None or an int in [1, %d] (the rows of a DQN minibatch, rl_learn_wide), got %r"
-                                 % (_lib.LEARN_WIDE_MAX, learn_batch))
+        elif learn_batch is not None:   # an int is the DQN learners' batch
+            limit = getattr(_lib, wide["DQN"].batch_max)
+            if isinstance(learn_batch, bool) or not isinstance(learn_batch, (int, np.integer)) or not 1 <= learn_batch <= limit:
+                raise ValueError("learn_batch must be None or an int in [1, %d] (the rows of a DQN minibatch, %s), got %r" % (limit, wide["DQN"].name, learn_batch))
             if learn != "device":
                 raise ValueError("learn_batch needs learn='device' (got learn=%r)" % (learn,))
             if "DQN" not in self.learn_kinds or not any(getattr(b, "method", None) == "DQN" for b in brains):
@@ -365,40 +346,27 @@ class Environment:
         if learn == "device":
             # the replay rings of DQN.py:15 (buffer_limit), filled inside the multi-tick launches; one learner per brain rl_learn trains,
             # whose packed tensor IS that brain's acting weights from here on (rl_learn rewrites it in place)
-            from ..learn import BUFFER_LIMIT, DeviceLearner, entry_of
-            entries = {k: entry_of(b.kind) for k, b in enumerate(brains) if b.method in self.learn_kinds}
-            entries = {k: e for k, e in entries.items() if e is not None}
-            prio = [k for k, b in enumerate(brains) if self.learn_prioritized and b.method == "PERD3QN"]
-            ppo = [k for k, b in enumerate(brains) if self.learn_rollout and b.method == "PPO"]
-            td = [k for k, b in enumerate(brains) if self.learn_td_priority and b.method == "PERDQN"]
-            prob = {"with_prob": True} if ppo else {}   # the acting probability of every row (PPO.py:73): only where a PPO brain learns
-            if prio or td or any(e == "rl_learn_dueling" for e in entries.values()):
-                # a D3QN or prioritised PERD3QN learner's ring holds its brain's `capacity` rows (D3QN.py:62, PERD3QN.py:49, 55: 10,000), a
-                # PERDQN learner's its brain's memory_size (20,000); every other ring stays DQN.py:15's
-                self.worlds.enable_capture([int(b.memory_size) if k in td else int(b.capacity) if (entries.get(k) == "rl_learn_dueling" or k in prio)
-                                            else BUFFER_LIMIT for k, b in enumerate(brains)], **prob)
-            else:
-                self.worlds.enable_capture(BUFFER_LIMIT, **prob)
-            for k in entries:
-                wide = ({"wide_batch": self.learn_batch_of["DQN"]} if self.learn_batch_of["DQN"] is not None and entries[k] == "rl_learn" else
-                        {"dueling_batch": self.learn_batch_of["D3QN"]} if self.learn_batch_of["D3QN"] is not None and entries[k] == "rl_learn_dueling" else {})
-                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], **wide)
-            pwide = {"prioritized_batch": self.learn_batch_of["PERD3QN"]} if self.learn_batch_of["PERD3QN"] is not None else {}
-            for k in prio:
-                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], prioritized=True, **pwide)
-            for k in ppo:
-                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], rollout=True)
-            for k in td:
-                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], td_priority=True)
+            plan = {k: ENTRY[entry_of(b.kind)] for k, b in enumerate(brains) if b.method in self.learn_kinds and entry_of(b.kind)}
+            for e in ENTRIES:   # ... and the explicit opt-ins (learn_prioritized, learn_rollout, learn_td_priority), in the table's order
+                if e.keyword and not e.narrow and getattr(self, "learn_" + e.keyword):
+                    plan.update({k: e for k, b in enumerate(brains) if b.method == e.method})
+            prob = {"with_prob": True} if any(e.family == "ppo" for e in plan.values()) else {}   # the acting probability of every row (PPO.py:73): only where a PPO brain learns
+            # a D3QN or prioritised PERD3QN learner's ring holds its brain's `capacity` rows (D3QN.py:62, PERD3QN.py:49, 55: 10,000), a
+            # PERDQN learner's its brain's memory_size (20,000); every other ring stays DQN.py:15's
+            rows = [int(getattr(b, plan[k].ring_rows)) if k in plan and plan[k].ring_rows else BUFFER_LIMIT for k, b in enumerate(brains)]
+            self.worlds.enable_capture(rows if any(e.ring_rows for e in plan.values()) else BUFFER_LIMIT, **prob)
+            for k, e in plan.items():   # (learn_batch: the wide entry in the narrow one's place, through its own keyword on top)
+                kw = {e.keyword: True} if e.keyword else {}
+                if self.learn_batch_of.get(e.method) is not None:
+                    kw[wide[e.method].keyword] = self.learn_batch_of[e.method]
+                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=self.worlds.replays[k], **kw)
             if not self.learners:
                 raise ValueError("learn='device': none of the brains is of a kind rl_learn trains (DQN)" if self.learn_kinds == ("DQN",) else
                                  "learn='device': none of the brains is of a kind in learn_kinds %r" % (self.learn_kinds,))
             # the default period is the smallest train_freq of the learners a run has WITHOUT learn_prioritized, so that the keyword does
             # not move their schedule; the prioritised learners' own train_freq counts only where they are the only learners -- and
             # likewise learn_rollout and the PPO learners', and learn_td_priority and the PERDQN learners'
-            timed = ([l for l in self.learners.values() if l.entry not in ("rl_learn_prioritized", "rl_learn_prioritized_wide", "rl_learn_ppo", "rl_learn_td")]
-                     or [l for l in self.learners.values() if l.entry not in ("rl_learn_ppo", "rl_learn_td")]
-                     or [l for l in self.learners.values() if l.entry != "rl_learn_td"] or list(self.learners.values()))
+            timed = next(t for t in ([l for l in self.learners.values() if l.spec.family in FAMILIES[:i]] for i in range(2, len(FAMILIES) + 1)) if t)
             self.learn_every = int(learn_every) if learn_every is not None else min(l.train_freq for l in timed)
             frozen = ["%d (%s)" % (k, b.method) for k, b in enumerate(brains) if k not in self.learners]
             if frozen:
@@ -410,6 +378,18 @@ class Environment:
         elif training:
             warn_inference_only()
 
+    def _opt_in(self, keyword, value, learn, brains):
+        """learn_<keyword>=True, the environment's spelling of DeviceLearner(..., <keyword>=True): None or True, with learn='device' and
+        at least one brain of the method that entry point trains."""
+        name, method = "learn_" + keyword, next(e.method for e in ENTRIES if e.keyword == keyword)
+        if value not in (None, True):
+            raise ValueError("%s must be None or True, got %r" % (name, value))
+        if value and learn != "device":
+            raise ValueError("%s=True needs learn='device' (got learn=%r)" % (name, learn))
+        if value and not any(getattr(b, "method", None) == method for b in brains):
+            raise ValueError("%s=True needs at least one Models.%s brain (got %s)" % (name, method, ", ".join(str(getattr(b, "method", b)) for b in brains)))
+        setattr(self, name, bool(value))
+
     def _align_learners(self):
         """Set-up of learn_ranks="average": the ranks build their brains from their own torch generators, so they start from rank 0's
         parameters -- one signature gather (the same learners, with the same exploration and soft_update_freq, on the same schedule everywhere,
@@ -420,13 +400,11 @@ class Environment:
             return
         from ..distributed import broadcast_from_rank0, check_learner_signature
         ls = [self.learners[k] for k in sorted(self.learners)]
-        entries = ("rl_learn", "rl_learn_dueling", "rl_learn_prioritized", "rl_learn_ppo", "rl_learn_td", "rl_learn_wide", "rl_learn_dueling_wide",
-                   "rl_learn_prioritized_wide")   # (new entries go to the END: the signatures of runs without them stay what they were)
         sig = [len(ls)]
         for k in sorted(self.learners):
             l = self.learners[k]   # (exploration and soft_update_freq decide whether a learner is called and when its target is synced)
-            sig += [k, l.kind, entries.index(l.entry), getattr(l, "exploration", 0), getattr(l, "soft_update_freq", 0)]
-            if l.entry in ("rl_learn_wide", "rl_learn_dueling_wide", "rl_learn_prioritized_wide"):   # (the other entry points' batches come from the brains' classes: the signatures of runs without learn_batch stay what they were)
+            sig += [k, l.kind, ENTRIES.index(l.spec), getattr(l, "exploration", 0), getattr(l, "soft_update_freq", 0)]
+            if l.spec.narrow:   # (the other entry points' batches come from the brains' classes: the signatures of runs without learn_batch stay what they were)
                 sig += [l.batch]
         sig += [self.learn_every, self.learn_steps_of["DQN"], self.learn_steps_of["D3QN"], self.learn_steps_of["PERDQN"], self.rollout_steps]
         check_learner_signature(sig, self.dist, device=self.worlds.device)
@@ -735,68 +713,78 @@ class Environment:
             agents = [SavedAgent(int(self.max_gene), self.brains[int(b)]) for b in bb]
         return Saver(main_folder, google_colab=self.google_colab).save(agents, self.static_families, self.tracker.results, settings)
 
+    # _weights_note: per entry point, in the notes' order, its note and whether it makes the frozen brains' note say "in this run"
+    _NOTES = {
+        "rl_learn_wide": (False, "%(steps)d minibatch updates of batch %(wide)d (learn_batch) every %(every)d episodes, rows drawn by content key with replacement"),
+        "rl_learn_dueling_wide": (False, "%(steps)d minibatch update(s) of batch %(wide)d (learn_batch) in 64-row tiles, the "
+                                  "advantage mean taken over the whole batch, every %(every)d episodes once past the brain's exploration, target synced every "
+                                  "soft_update_freq episodes, rows drawn by content key with replacement"),
+        "rl_learn": (False, "%(steps)d minibatch updates every %(every)d episodes, rows drawn by content key with replacement"),
+        "rl_learn_dueling": (True, "%(steps)d minibatch update(s) of batch %(batch)s every %(every)d episodes once past the brain's "
+                             "exploration, target synced every soft_update_freq episodes, rows drawn by content key with replacement"),
+        "rl_learn_prioritized": (True, "one minibatch update of batch %(batch)s every %(every)d episodes once past the brain's "
+                                 "exploration, target synced every soft_update_freq episodes, rows drawn with probability priority^0.6 / sum by content key "
+                                 "with replacement; rows appended between two calls get the priority maximum as of the earlier call"),
+        "rl_learn_prioritized_wide": (True, "one minibatch update of batch %(wide)d (learn_batch) in 64-row tiles, the "
+                                      "advantage mean taken over the whole batch and the priorities of all its rows rewritten, every %(every)d episodes once past the "
+                                      "brain's exploration, target synced every soft_update_freq episodes, rows drawn with probability priority^0.6 / sum by "
+                                      "content key with replacement; rows appended between two calls get the priority maximum as of the earlier call"),
+        "rl_learn_ppo": (True, "%(steps)d rollout(s) of %(batch)s rows, %(k_epoch)s Adam steps each, every %(every)d episodes; the rows are "
+                         "drawn by content key with replacement from those appended since the last call, so the GAE's neighbours are unrelated rows "
+                         "and the other fresh rows go unused"),
+        "rl_learn_td": (True, "%(steps)d minibatch update(s) of batch %(batch)s every %(every)d episodes once the ring holds the "
+                        "brain's train_start rows, loss scaled by the mean importance weight, target synced at every call, rows drawn with "
+                        "probability priority / sum by content key with replacement -- independent draws, not the reference's stratified ones; "
+                        "every new row gets the reference's one priority (0 + 0.01) ** 0.6; epsilon decays once per update"),
+    }
+    assert set(_NOTES) == set(ENTRY), "every row of learn.ENTRIES needs its note"
+
+    def _steps(self, family):
+        """The updates (PPO: rollouts) one learning call makes for the learners of `family`."""
+        return {"dqn": self.learn_steps, "dueling": self.learn_steps_of["D3QN"], "prioritized": 1, "ppo": self.rollout_steps,
+                "td": self.learn_steps_of["PERDQN"]}[family]
+
     def _weights_note(self):
         if not self.learners:
             return "as loaded / initialised -- reinlife_amd runs inference only, learn() is a no-op"
         frozen = [k for k in range(len(self.brains)) if k not in self.learners]
-        dqn = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn")
-        duel = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_dueling")
-        prio = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_prioritized")
-        wide = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_wide")
-        dwide = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_dueling_wide")
+        by = {name: [k for k in sorted(self.learners) if self.learners[k].spec is ENTRY[name]] for name in self._NOTES}
         note = []
-        if wide:
-            note.append("brains %s trained on the device (rl_learn_wide: %d minibatch updates of batch %d (learn_batch) every %d episodes, rows drawn by "
-                        "content key with replacement)" % (wide, self.learn_steps, self.learn_batch_of["DQN"], self.learn_every))
-        if dwide:
-            note.append("brains %s trained on the device (rl_learn_dueling_wide: %d minibatch update(s) of batch %d (learn_batch) in 64-row tiles, the "
-                        "advantage mean taken over the whole batch, every %d episodes once past the brain's exploration, target synced every "
-                        "soft_update_freq episodes, rows drawn by content key with replacement)"
-                        % (dwide, self.learn_steps_of["D3QN"], self.learn_batch_of["D3QN"], self.learn_every))
-        if dqn:
-            note.append("brains %s trained on the device (rl_learn: %d minibatch updates every %d episodes, rows drawn by content key with replacement)"
-                        % (dqn, self.learn_steps, self.learn_every))
-        if duel:
-            note.append("brains %s trained on the device (rl_learn_dueling: %d minibatch update(s) of batch %s every %d episodes once past the brain's "
-                        "exploration, target synced every soft_update_freq episodes, rows drawn by content key with replacement)"
-                        % (duel, self.learn_steps_of["D3QN"], sorted({self.learners[k].batch for k in duel}), self.learn_every))
-        if prio:
-            note.append("brains %s trained on the device (rl_learn_prioritized: one minibatch update of batch %s every %d episodes once past the brain's "
-                        "exploration, target synced every soft_update_freq episodes, rows drawn with probability priority^0.6 / sum by content key "
-                        "with replacement; rows appended between two calls get the priority maximum as of the earlier call)"
-                        % (prio, sorted({self.learners[k].batch for k in prio}), self.learn_every))
-        pwide = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_prioritized_wide")
-        if pwide:
-            note.append("brains %s trained on the device (rl_learn_prioritized_wide: one minibatch update of batch %d (learn_batch) in 64-row tiles, the "
-                        "advantage mean taken over the whole batch and the priorities of all its rows rewritten, every %d episodes once past the "
-                        "brain's exploration, target synced every soft_update_freq episodes, rows drawn with probability priority^0.6 / sum by "
-                        "content key with replacement; rows appended between two calls get the priority maximum as of the earlier call)"
-                        % (pwide, self.learn_batch_of["PERD3QN"], self.learn_every))
-        ppo = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_ppo")
-        if ppo:
-            note.append("brains %s trained on the device (rl_learn_ppo: %d rollout(s) of %s rows, %s Adam steps each, every %d episodes; the rows are "
-                        "drawn by content key with replacement from those appended since the last call, so the GAE's neighbours are unrelated rows "
-                        "and the other fresh rows go unused)"
-                        % (ppo, self.rollout_steps, sorted({self.learners[k].batch for k in ppo}), sorted({self.learners[k].k_epoch for k in ppo}), self.learn_every))
-        td = sorted(k for k, l in self.learners.items() if l.entry == "rl_learn_td")
-        if td:
-            note.append("brains %s trained on the device (rl_learn_td: %d minibatch update(s) of batch %s every %d episodes once the ring holds the "
-                        "brain's train_start rows, loss scaled by the mean importance weight, target synced at every call, rows drawn with "
-                        "probability priority / sum by content key with replacement -- independent draws, not the reference's stratified ones; "
-                        "every new row gets the reference's one priority (0 + 0.01) ** 0.6; epsilon decays once per update)"
-                        % (td, self.learn_steps_of["PERDQN"], sorted({self.learners[k].batch for k in td}), self.learn_every))
+        for name, ks in by.items():
+            if ks:
+                ls = [self.learners[k] for k in ks]
+                note.append("brains %s trained on the device (%s: %s)" % (ks, name, self._NOTES[name][1] % dict(
+                    steps=self._steps(ENTRY[name].family), batch=sorted({l.batch for l in ls}), wide=self.learn_batch_of.get(ENTRY[name].method),
+                    k_epoch=sorted({getattr(l, "k_epoch", None) for l in ls}), every=self.learn_every)))
         if frozen:
-            note.append("brains %s as loaded / initialised (their kinds do not learn in this run)" % frozen if (duel or prio or pwide or ppo or td) else
-                        "brains %s as loaded / initialised (their kinds do not learn in this build)" % frozen)
-        if self.learn_draw == "rank" and (wide or dqn or duel or dwide):
+            note.append("brains %s as loaded / initialised (their kinds do not learn in this %s)"
+                        % (frozen, "run" if any(ks and self._NOTES[name][0] for name, ks in by.items()) else "build"))
+        uniform = sorted(k for name, ks in by.items() if not ENTRY[name].draw for k in ks)
+        if self.learn_draw == "rank" and uniform:
             note.append("the minibatches of brains %s drawn by content-key rank (learn_draw='rank', rl_learn_draw_rank: the ring's rows sorted by "
                         "content key, draw d the row at rank (x_d * size) >> 32 -- uniform with replacement, other rows than rl_learn_draw names)"
-                        % sorted(wide + dqn + duel + dwide))
+                        % uniform)
         if self.learn_ranks:
             note.append("%d rank(s) trained independently on their own rings and averaged params, adam_m and adam_v over the ranks with the "
                         "highest step count after every learning episode (learn_ranks='average': periodic parameter averaging, this build's own)"
                         % self.world_size)
         return "; ".join(note)
+
+    def _decay_epsilon(self, ls, n):
+        """train_model()'s epsilon decay on the host, once per update the PERDQN learners `ls` made in a call of `n` steps."""
+        for l in ls:
+            if not l.trained_from:   # (a read-back: only until the ring first holds train_start rows)
+                l.trained_from = min(int(l.ring["count"].item()), int(l.ring["state"].shape[0])) >= l.train_start
+            if l.trained_from:       # train_model(): epsilon loses epsilon_decay at the start of every update while above epsilon_min
+                for _ in range(n):
+                    if l.brain.epsilon > l.brain.epsilon_min:
+                        l.brain.epsilon -= l.brain.epsilon_decay
+
+    # learn_now, per family in learn.FAMILIES' order: D3QNAgent.learn's schedule (the exploration gate and the target rule)?  the draw
+    # (None: the uniform draws, draw_slots or draw_slots_rank); one call per batch size (else ONE call)?  what follows a call
+    _SCHEDULE = (("dqn", False, None, False, None), ("dueling", True, None, True, None), ("prioritized", True, "draw_prioritized", True, None),
+                 ("ppo", False, "draw_rollout", False, None), ("td", False, "draw_td", True, _decay_epsilon))
+    assert tuple(s[0] for s in _SCHEDULE) == FAMILIES
 
     def learn_now(self, last=None):
         """One DQNAgent.train() (DQN.py:80-83) for every DQN learner, queued behind the ticks launched so far (DeviceWorlds.learn).  The
@@ -838,46 +826,19 @@ class Environment:
         self.learn_now_calls += 1
         called = []
         draw_slots = self.worlds.draw_slots_rank if self.learn_draw == "rank" else self.worlds.draw_slots
-        dqn = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry in ("rl_learn", "rl_learn_wide")]   # (learn_batch: all wide)
-        if dqn:
-            self.worlds.learn(dqn, self.learn_steps, slots=draw_slots(dqn, self.learn_steps))
-            called += dqn
-        duel = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry in ("rl_learn_dueling", "rl_learn_dueling_wide")   # (learn_batch naming D3QN: all wide)
-                and (last is None or last > self.learners[k].exploration)]
-        n = self.learn_steps_of["D3QN"]
-        for batch in sorted({l.batch for l in duel}):   # (one call per batch size: a call's slot table is rectangular)
-            ls = [l for l in duel if l.batch == batch]
-            if last is not None:
-                for l in ls:
-                    l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
-            self.worlds.learn(ls, n, slots=draw_slots(ls, n))
-            called += ls
-        prio =[self.learners[k] for k in sorted(self.learners) if self.learners[k].entry in ("rl_learn_prioritized", "rl_learn_prioritized_wide")   # (learn_batch naming PERD3QN: all wide)
-                and (last is None or last > self.learners[k].exploration)]
-        for batch in sorted({l.batch for l in prio}):
-            ls = [l for l in prio if l.batch == batch]
-            if last is not None:
-                for l in ls:
-                    l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
-            self.worlds.learn(ls, 1, slots=self.worlds.draw_prioritized(ls, 1))
-            called += ls
-        ppo = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_ppo"]
-        if ppo:
-            self.worlds.learn(ppo, self.rollout_steps, slots=self.worlds.draw_rollout(ppo, self.rollout_steps))
-            called += ppo
-        td = [self.learners[k] for k in sorted(self.learners) if self.learners[k].entry == "rl_learn_td"]
-        n = self.learn_steps_of["PERDQN"]
-        for batch in sorted({l.batch for l in td}):
-            ls = [l for l in td if l.batch == batch]
-            self.worlds.learn(ls, n, slots=self.worlds.draw_td(ls, n))
-            called += ls
-            for l in ls:
-                if not l.trained_from:   # (a read-back: only until the ring first holds train_start rows)
-                    l.trained_from = min(int(l.ring["count"].item()), int(l.ring["state"].shape[0])) >= l.train_start
-                if l.trained_from:       # train_model(): epsilon loses epsilon_decay at the start of every update while above epsilon_min
-                    for _ in range(n):
-                        if l.brain.epsilon > l.brain.epsilon_min:
-                            l.brain.epsilon -= l.brain.epsilon_decay
+        for family, scheduled, draw, per_batch, after in self._SCHEDULE:   # (learn_batch: a family's learners are all wide, or none is)
+            ls = [self.learners[k] for k in sorted(self.learners) if self.learners[k].spec.family == family
+                  and (not scheduled or last is None or last > self.learners[k].exploration)]
+            n = self._steps(family)
+            # (one call per batch size: a call's slot table is rectangular)
+            for ls in ([[l for l in ls if l.batch == batch] for batch in sorted({l.batch for l in ls})] if per_batch else [ls] if ls else []):
+                if scheduled and last is not None:
+                    for l in ls:
+                        l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
+                self.worlds.learn(ls, n, slots=getattr(self.worlds, draw)(ls, n) if draw else draw_slots(ls, n))
+                called += ls
+                if after:
+                    after(self, ls, n)
         if self.learn_ranks:
             self._merge_learners(called)
 

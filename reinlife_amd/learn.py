@@ -47,6 +47,7 @@ key, with replacement (DeviceWorlds.draw_td); the schedule is the caller's (once
 update made, not once per agent trigger -- a smaller explore_step restores the reference's rate in wall-clock terms."""
 import copy
 import ctypes as C
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -54,129 +55,154 @@ import torch
 from . import _lib
 
 GAMMA, BATCH, MIN_SIZE, BUFFER_LIMIT = 0.98, 32, 1000, 50_000   # DQN.py:14-16, 81
-ENTRY_BY_METHOD = {"DQN": "rl_learn", "D3QN": "rl_learn_dueling"}   # the brain kinds an entry point trains (Environment's learn_kinds)
+FAMILIES = ("dqn", "dueling", "prioritized", "ppo", "td")   # in Environment.learn_now's order of calls
+# what sync_to_module writes: the module of the parameters and the module of the target network (None: none), per family
+MODULES = {"dqn": ("agent", "target"), "dueling": ("eval_net", "target_net"), "prioritized": ("eval_net", "target_net"),
+           "ppo": ("model", None), "td": ("model", "target_model")}
+# the learner tensors a side struct is made of: (one per ring row?, dtype, what a fresh one holds)
+SIDE_TENSORS = {"priority": (True, torch.float32, 0), "weight": (True, torch.float32, 0), "keys": (True, torch.int64, 0),
+                "prio_max": (False, torch.float32, 1.0),   # PERD3QN.py:147
+                "seen": (False, torch.int64, 0), "fresh": (False, torch.int64, 0), "beta_is": (False, torch.float64, 0.4)}   # Memory.beta
+
+
+class Entry(NamedTuple):
+    """One C entry point that trains brains, and all the Python layer knows about it: DeviceLearner, DeviceWorlds.learn / draw_* and
+    Environment read these rows and compare no entry names."""
+    name: str
+    method: str                      # the brain method it trains
+    family: str                      # one of FAMILIES: hyperparameters, gates, Environment.learn_now's schedule, sync_to_module's modules
+    has_target: bool = True
+    ring_rows: str = None            # the brain attribute that sizes its replay ring (None: BUFFER_LIMIT)
+    keyword: str = None              # the DeviceLearner keyword that selects it (None: entry_of() does); Environment's is "learn_" + keyword
+    conflicts: tuple = ()            # the keywords that keyword excludes, in the order its message names them
+    needs: str = None                # the keyword that keyword goes on top of
+    narrow: str = None               # a wide entry: the entry it stands in for (the keyword is then the batch, Environment's learn_batch)
+    batch_max: str = None            # ... and the name of its batch limit in _lib
+    one_batch: bool = False          # DeviceWorlds.learn refuses unequal batches itself (elsewhere the C library answers)
+    side: type = None                # the struct it passes beside the rings: _lib.Prio, _lib.Ppo or _lib.TdPrio
+    side_tensors: tuple = ()         # ... and the learner tensors that struct is made of (SIDE_TENSORS)
+    draw: str = None                 # its own draw entry (None: the uniform draws, draw_slots / draw_slots_rank)
+    launches: Callable = lambda n_steps: 1   # what one call of n_steps counts as
+
+    supported = property(lambda e: e.name + "_supported")
+    work_bytes = property(lambda e: e.name + "_work_bytes" if e.narrow else None)
+
+
+_PRIO = dict(side=_lib.Prio, side_tensors=("priority", "weight", "keys", "prio_max", "seen"))
+# A row's index is part of the learner signature the ranks compare (Environment._align_learners): new entries go to the END.  The keyword
+# rows are tried last to first (DeviceLearner), so a new opt-in is checked before the older ones it names as conflicts.
+ENTRIES = (
+    Entry("rl_learn", "DQN", "dqn"),
+    Entry("rl_learn_dueling", "D3QN", "dueling", ring_rows="capacity"),
+    Entry("rl_learn_prioritized", "PERD3QN", "prioritized", ring_rows="capacity", keyword="prioritized", draw="rl_learn_prioritized_draw", **_PRIO),
+    Entry("rl_learn_ppo", "PPO", "ppo", has_target=False, keyword="rollout", conflicts=("prioritized",),
+          side=_lib.Ppo, side_tensors=("keys", "seen", "fresh"), draw="rl_learn_rollout"),
+    Entry("rl_learn_td", "PERDQN", "td", ring_rows="memory_size", keyword="td_priority", conflicts=("prioritized", "rollout"),
+          side=_lib.TdPrio, side_tensors=("priority", "keys", "seen", "beta_is"), draw="rl_learn_td_draw"),
+    Entry("rl_learn_wide", "DQN", "dqn", keyword="wide_batch", conflicts=("prioritized", "rollout", "td_priority"),
+          narrow="rl_learn", batch_max="LEARN_WIDE_MAX", launches=lambda n_steps: 2 * n_steps + 3),   # check, tiles and update per step, target / counters, pack
+    Entry("rl_learn_dueling_wide", "D3QN", "dueling", ring_rows="capacity", keyword="dueling_batch",
+          conflicts=("wide_batch", "prioritized", "rollout", "td_priority"), narrow="rl_learn_dueling", batch_max="LEARN_DUELING_WIDE_MAX",
+          one_batch=True, launches=lambda n_steps: 3 * n_steps + 3),   # check, the two tile passes and the update per step, target / counters, pack
+    Entry("rl_learn_prioritized_wide", "PERD3QN", "prioritized", ring_rows="capacity", keyword="prioritized_batch", needs="prioritized",
+          conflicts=("wide_batch", "dueling_batch", "rollout", "td_priority"), narrow="rl_learn_prioritized",
+          batch_max="LEARN_PRIORITIZED_WIDE_MAX", one_batch=True, draw="rl_learn_prioritized_wide_draw",
+          launches=lambda n_steps: 3 * n_steps + 3, **_PRIO),   # as rl_learn_dueling_wide
+)
+ENTRY = {e.name: e for e in ENTRIES}
+ENTRY_BY_METHOD = {e.method: e.name for e in ENTRIES if not e.keyword}   # the brain kinds an entry point trains without a keyword (Environment's learn_kinds)
+assert all(e.family in FAMILIES and set(e.side_tensors) <= set(SIDE_TENSORS) for e in ENTRIES) and set(ENTRY_BY_METHOD.values()) <= set(ENTRY)
 
 
 def entry_of(kind):
     """The name of the C entry point that trains brains of `kind`, or None."""
     lib = _lib.lib()
-    return "rl_learn" if lib.rl_learn_supported(kind) else "rl_learn_dueling" if lib.rl_learn_dueling_supported(kind) else None
+    return next((name for name in ENTRY_BY_METHOD.values() if getattr(lib, ENTRY[name].supported)(kind)), None)
+
+
+def _spelled(keyword):
+    return keyword if keyword.endswith("_batch") else keyword + "=True"
 
 
 class DeviceLearner:
     def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False, td_priority=False, prioritized_batch=None, wide_batch=None, dueling_batch=None):
         lib = _lib.lib()
-        if prioritized_batch is not None:   # an explicit opt-in on top of prioritized=True: the prioritised learner on wide minibatches
-            other = (" with wide_batch" if wide_batch is not None else " with dueling_batch" if dueling_batch is not None else " with rollout=True" if rollout
-                     else " with td_priority=True" if td_priority else "" if prioritized else " without prioritized=True")
-            if other or not lib.rl_learn_prioritized_wide_supported(brain.kind):
-                raise ValueError("prioritized_batch is for PERD3QN brains with prioritized=True (rl_learn_prioritized_wide); got a %s brain (kind %d)%s"
-                                 % (brain.method, brain.kind, other))
-            if (isinstance(prioritized_batch, bool) or not isinstance(prioritized_batch, (int, np.integer))
-                    or not 1 <= prioritized_batch <= _lib.LEARN_PRIORITIZED_WIDE_MAX):
-                raise ValueError("prioritized_batch must be an int in [1, %d] (the rows of a minibatch of rl_learn_prioritized_wide), got %r"
-                                 % (_lib.LEARN_PRIORITIZED_WIDE_MAX, prioritized_batch))
-            self.entry = "rl_learn_prioritized_wide"
-        elif dueling_batch is not None:   # an explicit opt-in, like the four below: entry_of() and ENTRY_BY_METHOD keep answering what they answered
-            other = (" with wide_batch" if wide_batch is not None else " with prioritized=True" if prioritized else " with rollout=True" if rollout
-                     else " with td_priority=True" if td_priority else "")
-            if other or not lib.rl_learn_dueling_wide_supported(brain.kind):
-                raise ValueError("dueling_batch is for D3QN brains (rl_learn_dueling_wide); got a %s brain (kind %d)%s" % (brain.method, brain.kind, other))
-            if isinstance(dueling_batch, bool) or not isinstance(dueling_batch, (int, np.integer)) or not 1 <= dueling_batch <= _lib.LEARN_DUELING_WIDE_MAX:
-                raise ValueError("dueling_batch must be an int in [1, %d] (the rows of a minibatch of rl_learn_dueling_wide), got %r"
-                                 % (_lib.LEARN_DUELING_WIDE_MAX, dueling_batch))
-            self.entry = "rl_learn_dueling_wide"
-        elif wide_batch is not None:   # an explicit opt-in, like the three below: entry_of() and ENTRY_BY_METHOD keep answering what they answered
-            other = " with prioritized=True" if prioritized else " with rollout=True" if rollout else " with td_priority=True" if td_priority else ""
-            if other or not lib.rl_learn_wide_supported(brain.kind):
-                raise ValueError("wide_batch is for DQN brains (rl_learn_wide); got a %s brain (kind %d)%s" % (brain.method, brain.kind, other))
-            if isinstance(wide_batch, bool) or not isinstance(wide_batch, (int, np.integer)) or not 1 <= wide_batch <= _lib.LEARN_WIDE_MAX:
-                raise ValueError("wide_batch must be an int in [1, %d] (the rows of a minibatch of rl_learn_wide), got %r" % (_lib.LEARN_WIDE_MAX, wide_batch))
-            self.entry = "rl_learn_wide"
-        elif td_priority:   # an explicit opt-in, like prioritized and rollout: entry_of() and ENTRY_BY_METHOD keep answering what they answered
-            if prioritized or rollout or not lib.rl_learn_td_supported(brain.kind):
-                raise ValueError("td_priority=True is for PERDQN brains (rl_learn_td); got a %s brain (kind %d)%s"
-                                 % (brain.method, brain.kind, " with prioritized=True" if prioritized else " with rollout=True" if rollout else ""))
-            self.entry = "rl_learn_td"
-        elif rollout:   # an explicit opt-in, like prioritized: entry_of() and ENTRY_BY_METHOD keep answering what they answered
-            if prioritized or not lib.rl_learn_ppo_supported(brain.kind):
-                raise ValueError("rollout=True is for PPO brains (rl_learn_ppo); got a %s brain (kind %d)%s"
-                                 % (brain.method, brain.kind, " with prioritized=True" if prioritized else ""))
-            self.entry = "rl_learn_ppo"
-        elif prioritized:   # an explicit opt-in: entry_of() and ENTRY_BY_METHOD keep answering what they answered
-            if not lib.rl_learn_prioritized_supported(brain.kind):
-                raise ValueError("prioritized=True is for PERD3QN brains (rl_learn_prioritized); got a %s brain (kind %d)" % (brain.method, brain.kind))
-            self.entry = "rl_learn_prioritized"
+        given = dict(prioritized=prioritized, rollout=rollout, td_priority=td_priority, prioritized_batch=prioritized_batch, wide_batch=wide_batch,
+                     dueling_batch=dueling_batch)
+        given = {k: v for k, v in given.items() if (v is not None if k.endswith("_batch") else v)}
+        # every keyword is an explicit opt-in: entry_of() and ENTRY_BY_METHOD keep answering what they answered
+        spec = next((e for e in reversed(ENTRIES) if e.keyword in given), None)
+        if spec is None:
+            spec = ENTRY.get(entry_of(brain.kind))
+            if spec is None:
+                raise ValueError("no entry point trains %s brains (kind %d): only DQN (rl_learn) and D3QN (rl_learn_dueling) learn on the device"
+                                 % (brain.method, brain.kind))
         else:
-            self.entry = entry_of(brain.kind)
-        if self.entry is None:
-            raise ValueError("no entry point trains %s brains (kind %d): only DQN (rl_learn) and D3QN (rl_learn_dueling) learn on the device"
-                             % (brain.method, brain.kind))
+            other = next((" with " + _spelled(k) for k in spec.conflicts if k in given), "")
+            if not other and spec.needs and spec.needs not in given:
+                other = " without " + _spelled(spec.needs)
+            if other or not getattr(lib, spec.supported)(brain.kind):
+                raise ValueError("%s is for %s brains%s (%s); got a %s brain (kind %d)%s" % (
+                    _spelled(spec.keyword), spec.method, " with " + _spelled(spec.needs) if spec.needs else "", spec.name, brain.method, brain.kind, other))
+            if spec.narrow:   # a wide entry: the narrow entry's learner with its own batch
+                batch, limit = given[spec.keyword], getattr(_lib, spec.batch_max)
+                if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or not 1 <= batch <= limit:
+                    raise ValueError("%s must be an int in [1, %d] (the rows of a minibatch of %s), got %r" % (spec.keyword, limit, spec.name, batch))
+        self.spec, self.entry = spec, spec.name
         from .worlds import pack_brain_weights
         self.brain, self.kind, self.device = brain, brain.kind, torch.device(device)
         flat = brain.state_dict_flat()
         self.n_params = int(lib.rl_policy_n_params(self.kind))
         self.merge_floats = int(lib.rl_learn_merge_floats(self.kind))   # this learner's segment of an exported row: params | adam_m | adam_v | step count
         self.params = torch.as_tensor(flat, device=self.device)
-        self.target = None if rollout else self.params.clone()  # DQN.py:50 / D3QN.py:60 (PPO has no target network)
+        self.target = self.params.clone() if spec.has_target else None  # DQN.py:50 / D3QN.py:60 (PPO has no target network)
         self.adam_m = torch.zeros_like(self.params)
         self.adam_v = torch.zeros_like(self.params)
         self.state = torch.zeros(2, dtype=torch.int64, device=self.device)   # [Adam steps taken, rl_learn calls made]
         self.packed = pack_brain_weights(self.kind, flat, self.device)
         self.train_freq = int(getattr(brain, "train_freq", 20))
-        if self.entry == "rl_learn_ppo":   # PPO.py:42-43: the brain's own hyperparameters
+        if spec.family == "ppo":   # PPO.py:42-43: the brain's own hyperparameters
             self.lr, self.gamma = float(getattr(brain, "learning_rate", 0.0005)), float(getattr(brain, "gamma", 0.98))
             self.lmbda, self.eps_clip, self.k_epoch = float(getattr(brain, "lmbda", 0.95)), float(getattr(brain, "eps_clip", 0.1)), int(getattr(brain, "k_epoch", 3))
             self.batch, self.min_size = _lib.PPO_ROLLOUT_MAX, 0  # the rows of a rollout; no size gate (an empty window makes no update)
             self.n_steps_default = 1                             # one PPO.learn() per call
             self.sync_target = False
-        elif self.entry == "rl_learn_td":   # PERDQNAgent.__init__: the brain's own hyperparameters
+        elif spec.family == "td":   # PERDQNAgent.__init__: the brain's own hyperparameters
             self.lr, self.gamma = float(getattr(brain, "learning_rate", 1e-3)), float(getattr(brain, "discount_factor", 0.99))
             self.batch = int(getattr(brain, "batch_size", 64))
             self.train_start, self.memory_size = int(getattr(brain, "train_start", 1000)), int(getattr(brain, "memory_size", 20000))
             self.min_size = self.train_start - 1                 # learn(): n_entries >= train_start
             self.n_steps_default = 1                             # train_model() makes one update
             self.sync_target = True                              # learn(): update_target_model() after every trigger
-        elif self.entry in ("rl_learn", "rl_learn_wide"):   # the wide learner is the DQN learner with its own batch
+        elif spec.family == "dqn":
             self.lr = float(getattr(brain, "learning_rate", 0.0005))
-            self.gamma, self.batch, self.min_size = GAMMA, BATCH if wide_batch is None else int(wide_batch), MIN_SIZE
+            self.gamma, self.batch, self.min_size = GAMMA, BATCH, MIN_SIZE
             self.n_steps_default = 5                             # DQN.py:143
             self.sync_target = True                              # DQN.py:83
         else:   # D3QN.py:54-72: the brain's own hyperparameters
             self.lr = float(getattr(brain, "learning_rate", 1e-3))
             self.gamma, self.batch = float(getattr(brain, "gamma", 0.99)), int(getattr(brain, "batch_size", 64))
             # random.sample needs `batch` rows (D3QN.py:98, 140): the only gate; np.random.choice (PERD3QN.py:165) needs one
-            self.min_size = 0 if prioritized else self.batch - 1
-            if dueling_batch is not None:   # the wide learner is the D3QN learner with its own batch: the gate stays the brain's (rows are drawn with replacement)
-                self.batch = int(dueling_batch)
-            if prioritized_batch is not None:   # likewise the prioritised learner: np.random.choice's gate (one row) stays
-                self.batch = int(prioritized_batch)
+            self.min_size = 0 if spec.family == "prioritized" else self.batch - 1
             self.exploration, self.soft_update_freq = int(getattr(brain, "exploration", 1000)), int(getattr(brain, "soft_update_freq", 200))
             self.n_steps_default = 1                             # D3QNAgent.train() makes one update
             self.sync_target = False                             # the schedule's (D3QN.py:125-126, Environment.learn_now)
+        if spec.narrow:   # the wide learner's own batch: the gate stays the brain's (rows are drawn with replacement)
+            self.batch = int(given[spec.keyword])
         self.beta1, self.beta2, self.eps = 0.9, 0.999, 1e-8      # torch.optim.Adam's defaults (DQN.py:52, D3QN.py:61)
         self.ring = ring          # the brain's replay ring: a dict of device tensors as DeviceWorlds.enable_capture() makes them
         self.alpha = 0.6          # PERD3QN.py:134
-        self.priority = self.weight = self.keys = self.prio_max = self.seen = None
-        if prioritized and ring is not None:
-            self._make_prio()
-        self.fresh = None         # rollout=True: the window's bookkeeping (seen and keys above, fresh here)
-        if rollout and ring is not None:
-            self._make_ppo()
         self.prio_e, self.prio_a, self.beta_increment = 0.01, 0.6, 0.001   # Memory.e, Memory.a, Memory.beta_increment_per_sampling
         self.p_new = float((torch.zeros(()) + self.prio_e) ** self.prio_a)  # append_sample's priority: float32 (0 + e) ** a, as torch makes it
-        self.beta_is = None       # td_priority=True: Memory.beta, a device double
+        # the side struct's tensors (SIDE_TENSORS): prioritized=True the memory's priorities, their maximum and the draw's scratch;
+        # rollout=True the window's bookkeeping; td_priority=True the memory's priorities and beta_is (Memory.beta, a device double)
+        self.priority = self.weight = self.keys = self.prio_max = self.seen = self.fresh = self.beta_is = None
         self.is_weight = None     # optional device float32 [n_steps, batch]: rl_learn_td's importance weights (tests, diagnostics)
         self.trained_from = False  # td_priority=True: the ring has reached train_start (Environment.learn_now reads it back until then)
-        if td_priority and ring is not None:
-            self._make_td()
-        self.work = None          # wide_batch: rl_learn_wide's scratch (header, the tiles' partial gradients and loss sums); needs no initialisation
-        if self.entry == "rl_learn_wide":
-            self.work = torch.empty(int(lib.rl_learn_wide_work_bytes(self.kind, self.batch)), dtype=torch.uint8, device=self.device)
-        if self.entry == "rl_learn_dueling_wide":   # dueling_batch: rl_learn_dueling_wide's scratch (header, partial gradients, advantage sums, per-row stash)
-            self.work = torch.empty(int(lib.rl_learn_dueling_wide_work_bytes(self.kind, self.batch)), dtype=torch.uint8, device=self.device)
-        if self.entry == "rl_learn_prioritized_wide":   # prioritized_batch: rl_learn_prioritized_wide's scratch (rl_learn_dueling_wide's layout)
-            self.work = torch.empty(int(lib.rl_learn_prioritized_wide_work_bytes(self.kind, self.batch)), dtype=torch.uint8, device=self.device)
+        if spec.side and ring is not None:
+            self._make_side()
+        # a wide entry's scratch (header, the tiles' partial gradients and sums, rl_learn_dueling_wide's per-row stash); needs no initialisation
+        self.work = torch.empty(int(getattr(lib, spec.work_bytes)(self.kind, self.batch)), dtype=torch.uint8, device=self.device) if spec.narrow else None
         self.rank_order = self.rank_work = None   # DeviceWorlds.draw_slots_rank: the ring's slots in key order, and rl_learn_draw_rank's scratch
         self.loss = None          # optional device float32 [n_steps]
         self.grad = None          # optional device float32 [n_steps, n_params] (tests, diagnostics)
@@ -197,61 +223,43 @@ class DeviceLearner:
         return _lib.Replay(*[p(r.get(n)) for n in ("state", "state_prime", "action", "reward", "done", "prob", "age", "count")],
                            int(r["state"].shape[0]))
 
-    def _make_prio(self):
-        """The prioritised memory beside the ring (rl_prio), sized to it: no priorities yet, maximum 1.0 (PERD3QN.py:147), nothing seen."""
+    def _make_side(self):
+        """The memory beside the ring, sized to it -- rl_prio: no priorities yet, maximum 1.0, nothing seen; rl_tdprio: no priorities yet,
+        nothing seen, beta 0.4; rl_ppo, the on-policy window's bookkeeping: nothing seen, no fresh rows."""
         capacity = int(self.ring["state"].shape[0])
-        self.priority = torch.zeros(capacity, dtype=torch.float32, device=self.device)
-        self.weight = torch.zeros(capacity, dtype=torch.float32, device=self.device)
-        self.keys = torch.zeros(capacity, dtype=torch.int64, device=self.device)
-        self.prio_max = torch.ones(1, dtype=torch.float32, device=self.device)
-        self.seen = torch.zeros(1, dtype=torch.int64, device=self.device)
+        for name in self.spec.side_tensors:
+            per_row, dtype, fresh = SIDE_TENSORS[name]
+            setattr(self, name, torch.full((capacity if per_row else 1,), fresh, dtype=dtype, device=self.device))
+
+    _make_prio = _make_td = _make_ppo = _make_side   # (one implementation; the names it had per struct)
+
+    def side_struct(self, kind, gate=True):
+        """The struct of type `kind` that this learner's entry point takes beside the rings (Entry.side), its tensors made or re-made
+        to the ring's size."""
+        if self.spec.side is not kind:
+            raise _lib.ReinLifeHipError({_lib.Prio: "this DeviceLearner has no prioritised memory (DeviceLearner(..., prioritized=True))",
+                                         _lib.TdPrio: "this DeviceLearner has no PERDQN memory (DeviceLearner(..., td_priority=True))",
+                                         _lib.Ppo: "this DeviceLearner is no PPO learner (DeviceLearner(..., rollout=True))"}[kind])
+        if self.ring is None:
+            raise _lib.ReinLifeHipError("this DeviceLearner has no replay ring (DeviceLearner.ring)")
+        capacity = self.ring["state"].shape[0]
+        tensors = [(getattr(self, n), SIDE_TENSORS[n][0]) for n in self.spec.side_tensors]
+        if any(t is None or (per_row and t.numel() != capacity) for t, per_row in tensors):
+            self._make_side()
+        # a field is the learner attribute of its name (rl_tdprio's beta: beta_is); gate=False leaves rl_ppo's `fresh` out
+        field = lambda n: None if n == "fresh" and not gate else getattr(self, "beta_is" if n == "beta" else n)  # noqa: E731
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        return kind(*[p(field(n)) if ctype is C.c_void_p else field(n) for n, ctype in kind._fields_])
 
     def prio_struct(self):
-        if self.entry not in ("rl_learn_prioritized", "rl_learn_prioritized_wide"):
-            raise _lib.ReinLifeHipError("this DeviceLearner has no prioritised memory (DeviceLearner(..., prioritized=True))")
-        if self.ring is None:
-            raise _lib.ReinLifeHipError("this DeviceLearner has no replay ring (DeviceLearner.ring)")
-        if self.priority is None or self.priority.numel() != self.ring["state"].shape[0]:
-            self._make_prio()
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        return _lib.Prio(p(self.priority), p(self.weight), p(self.keys), p(self.prio_max), p(self.seen), self.alpha)
-
-    def _make_td(self):
-        """The PERDQN memory beside the ring (rl_tdprio), sized to it: no priorities yet, nothing seen, beta 0.4 (Memory.beta)."""
-        capacity = int(self.ring["state"].shape[0])
-        self.priority = torch.zeros(capacity, dtype=torch.float32, device=self.device)
-        self.keys = torch.zeros(capacity, dtype=torch.int64, device=self.device)
-        self.seen = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.beta_is = torch.full((1,), 0.4, dtype=torch.float64, device=self.device)
+        return self.side_struct(_lib.Prio)
 
     def td_struct(self):
-        if self.entry != "rl_learn_td":
-            raise _lib.ReinLifeHipError("this DeviceLearner has no PERDQN memory (DeviceLearner(..., td_priority=True))")
-        if self.ring is None:
-            raise _lib.ReinLifeHipError("this DeviceLearner has no replay ring (DeviceLearner.ring)")
-        if self.priority is None or self.priority.numel() != self.ring["state"].shape[0]:
-            self._make_td()
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        return _lib.TdPrio(p(self.priority), p(self.keys), p(self.seen), p(self.beta_is), self.p_new, self.prio_e, self.prio_a,
-                           self.beta_increment, p(self.is_weight))
-
-    def _make_ppo(self):
-        """The on-policy window's bookkeeping beside the ring (rl_ppo), sized to it: nothing seen, no fresh rows."""
-        capacity = int(self.ring["state"].shape[0])
-        self.keys = torch.zeros(capacity, dtype=torch.int64, device=self.device)
-        self.seen = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.fresh = torch.zeros(1, dtype=torch.int64, device=self.device)
+        return self.side_struct(_lib.TdPrio)
 
     def ppo_struct(self, gate=True):
         """rl_ppo.  gate=False leaves `fresh` out: rl_learn_ppo then trains on the slots it is given whatever the last rollout's window held."""
-        if self.entry != "rl_learn_ppo":
-            raise _lib.ReinLifeHipError("this DeviceLearner is no PPO learner (DeviceLearner(..., rollout=True))")
-        if self.ring is None:
-            raise _lib.ReinLifeHipError("this DeviceLearner has no replay ring (DeviceLearner.ring)")
-        if self.fresh is None or self.keys.numel() != self.ring["state"].shape[0]:
-            self._make_ppo()
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        return _lib.Ppo(self.lmbda, self.eps_clip, self.k_epoch, p(self.seen), p(self.fresh) if gate else None, p(self.keys))
+        return self.side_struct(_lib.Ppo, gate=gate)
 
     @property
     def steps(self):
@@ -271,21 +279,13 @@ class DeviceLearner:
         """The trained parameters into brain.agent and the target network's into brain.target (made on first use: a copy, no
         generator draw), so that Saver and state_dict() see them.  D3QN and PERD3QN: into brain.eval_net and brain.target_net; PERDQN: into
         brain.model and brain.target_model."""
-        if self.entry == "rl_learn_ppo":   # PPO.py:46: one module, no target
-            self._load(self.brain.model, self.params.cpu().numpy())
+        module, target = MODULES[self.spec.family]   # (PPO.py:46: one module, no target; PERDQNAgent: Saver reads model)
+        self._load(getattr(self.brain, module), self.params.cpu().numpy())
+        if target is None:
             return
-        if self.entry == "rl_learn_td":    # PERDQNAgent: model and target_model (Saver reads model)
-            self._load(self.brain.model, self.params.cpu().numpy())
-            self._load(self.brain.target_model, self.target.cpu().numpy())
-            return
-        if self.entry in ("rl_learn_dueling", "rl_learn_prioritized", "rl_learn_dueling_wide", "rl_learn_prioritized_wide"):
-            self._load(self.brain.eval_net, self.params.cpu().numpy())
-            self._load(self.brain.target_net, self.target.cpu().numpy())
-            return
-        self._load(self.brain.agent, self.params.cpu().numpy())
-        if getattr(self.brain, "target", None) is None:
-            self.brain.target = copy.deepcopy(self.brain.agent)
-        self._load(self.brain.target, self.target.cpu().numpy())
+        if getattr(self.brain, target, None) is None:
+            setattr(self.brain, target, copy.deepcopy(getattr(self.brain, module)))
+        self._load(getattr(self.brain, target), self.target.cpu().numpy())
 
 
 def philox_slots(seed, brain_index, calls, n_steps, batch, size):

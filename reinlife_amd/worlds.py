@@ -483,24 +483,7 @@ class DeviceWorlds:
         A list of wide prioritised learners (DeviceLearner(..., prioritized=True, prioritized_batch=B)) goes to
         rl_learn_prioritized_wide_draw: the same two launches and the same arithmetic for batches up to 2048 (B <= 64 with n_steps = 1:
         rl_learn_prioritized_draw's table).  The learners of a call are all of the one kind or all of the other."""
-        n = len(learners)
-        if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
-            raise ValueError("draw_prioritized(): 1 to %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
-        if len({l.batch for l in learners}) != 1:
-            raise ValueError("draw_prioritized(): the learners of a call must share one batch size")
-        if any(l.entry not in ("rl_learn_prioritized", "rl_learn_prioritized_wide") for l in learners):
-            raise ValueError("draw_prioritized(): every learner must be a prioritised one (DeviceLearner(..., prioritized=True))")
-        entries = {l.entry for l in learners}
-        if len(entries) != 1:
-            raise ValueError("draw_prioritized(): the learners of a call must be of one kind (one entry point), got %s" % sorted(entries))
-        draw = "rl_learn_prioritized_draw" if entries == {"rl_learn_prioritized"} else "rl_learn_prioritized_wide_draw"
-        arr = (_lib.Learner * n)(*[l.struct() for l in learners])
-        rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
-        prios = (_lib.Prio * n)(*[l.prio_struct() for l in learners])
-        slots = torch.zeros((n, int(n_steps), int(learners[0].batch)), dtype=torch.int32, device=self.device)
-        _lib.check(getattr(self.lib, draw)(self.handle, arr, rings, prios, n, int(n_steps), _ptr(slots), self._stream()), draw)
-        self.launches += 2
-        return slots
+        return self._draw_side("draw_prioritized", learners, n_steps, _lib.Prio, "a prioritised one (DeviceLearner(..., prioritized=True))")
 
     def draw_rollout(self, learners, n_steps):
         """The rollouts of PPO learners (DeviceLearner(..., rollout=True)) for learn(learners, n_steps, slots=...): the on-policy draw
@@ -508,20 +491,7 @@ class DeviceWorlds:
         holds); each of the n_steps * batch draws takes a window row uniformly, with replacement, by a key of the rows' content: the same
         rows whatever slots they sit in.  Leaves the number of rows of the window in learner.fresh (an empty one: the following learn()
         makes no update) and moves learner.seen up.  Device int32 [len(learners), n_steps, batch], queued on the current stream."""
-        n = len(learners)
-        if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
-            raise ValueError("draw_rollout(): 1 to %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
-        if len({l.batch for l in learners}) != 1:
-            raise ValueError("draw_rollout(): the learners of a call must share one batch size")
-        if any(l.entry != "rl_learn_ppo" for l in learners):
-            raise ValueError("draw_rollout(): every learner must be a PPO one (DeviceLearner(..., rollout=True))")
-        arr = (_lib.Learner * n)(*[l.struct() for l in learners])
-        rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
-        ppos = (_lib.Ppo * n)(*[l.ppo_struct() for l in learners])
-        slots = torch.zeros((n, int(n_steps), int(learners[0].batch)), dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.rl_learn_rollout(self.handle, arr, rings, ppos, n, int(n_steps), _ptr(slots), self._stream()), "rl_learn_rollout")
-        self.launches += 2
-        return slots
+        return self._draw_side("draw_rollout", learners, n_steps, _lib.Ppo, "a PPO one (DeviceLearner(..., rollout=True))")
 
     def draw_td(self, learners, n_steps):
         """The minibatches of PERDQN learners (DeviceLearner(..., td_priority=True)) for learn(learners, n_steps, slots=...): the draw of
@@ -529,18 +499,26 @@ class DeviceWorlds:
         append_sample gives (learner.p_new), then each draw takes a row with probability priority / sum, with replacement, by a key of the
         rows' content: the same rows whatever slots they sit in (the reference's sample() is stratified through its sum tree; here the
         draws are independent).  Device int32 [len(learners), n_steps, batch], queued on the current stream."""
+        return self._draw_side("draw_td", learners, n_steps, _lib.TdPrio, "a PERDQN one (DeviceLearner(..., td_priority=True))")
+
+    def _draw_side(self, who, learners, n_steps, side, one_of):
+        """draw_prioritized / draw_rollout / draw_td: the draw entry of the learners' own (Entry.draw), fed their side structs of type `side`."""
         n = len(learners)
         if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
-            raise ValueError("draw_td(): 1 to %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
+            raise ValueError("%s(): 1 to %d learners per call (got %d)" % (who, _lib.MAX_CAPTURE_BRAINS, n))
         if len({l.batch for l in learners}) != 1:
-            raise ValueError("draw_td(): the learners of a call must share one batch size")
-        if any(l.entry != "rl_learn_td" for l in learners):
-            raise ValueError("draw_td(): every learner must be a PERDQN one (DeviceLearner(..., td_priority=True))")
+            raise ValueError("%s(): the learners of a call must share one batch size" % who)
+        if any(l.spec.side is not side for l in learners):
+            raise ValueError("%s(): every learner must be %s" % (who, one_of))
+        entries = {l.entry for l in learners}
+        if len(entries) != 1:
+            raise ValueError("%s(): the learners of a call must be of one kind (one entry point), got %s" % (who, sorted(entries)))
+        draw = learners[0].spec.draw
         arr = (_lib.Learner * n)(*[l.struct() for l in learners])
         rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
-        tds = (_lib.TdPrio * n)(*[l.td_struct() for l in learners])
+        sides = (side * n)(*[l.side_struct(side) for l in learners])
         slots = torch.zeros((n, int(n_steps), int(learners[0].batch)), dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.rl_learn_td_draw(self.handle, arr, rings, tds, n, int(n_steps), _ptr(slots), self._stream()), "rl_learn_td_draw")
+        _lib.check(getattr(self.lib, draw)(self.handle, arr, rings, sides, n, int(n_steps), _ptr(slots), self._stream()), draw)
         self.launches += 2
         return slots
 
@@ -571,7 +549,7 @@ class DeviceWorlds:
         entries = {l.entry for l in learners}
         if len(entries) != 1:
             raise ValueError("learn(): the learners of a call must be of one kind (one entry point), got %s" % sorted(entries))
-        entry = entries.pop()
+        spec = learners[0].spec   # (the row of learn.ENTRIES: every C signature is handle, learners, rings, [side structs], n, n_steps, slots, [work], stream)
         if n > _lib.MAX_CAPTURE_BRAINS:
             raise ValueError("learn(): at most %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
         arr = (_lib.Learner * n)(*[l.struct() for l in learners])
@@ -582,36 +560,13 @@ class DeviceWorlds:
             slots = slots.to(device=self.device, dtype=torch.int32).contiguous()
             if slots.numel() != n * n_steps * learners[0].batch or len({l.batch for l in learners}) != 1:
                 raise ValueError("learn(): slots must hold [n_learners, n_steps, batch] = [%d, %d, %d] entries" % (n, n_steps, learners[0].batch))
-        if entry == "rl_learn_prioritized":
-            prios = (_lib.Prio * n)(*[l.prio_struct() for l in learners])
-            _lib.check(self.lib.rl_learn_prioritized(self.handle, arr, rings, prios, n, int(n_steps), _ptr(slots), self._stream()), entry)
-        elif entry == "rl_learn_prioritized_wide":
-            if len({l.batch for l in learners}) != 1:
-                raise ValueError("learn(): the rl_learn_prioritized_wide learners of a call must share one batch size, got %s" % sorted({l.batch for l in learners}))
-            prios = (_lib.Prio * n)(*[l.prio_struct() for l in learners])
-            work = (C.c_void_p * n)(*[l.work.data_ptr() for l in learners])
-            _lib.check(self.lib.rl_learn_prioritized_wide(self.handle, arr, rings, prios, n, int(n_steps), _ptr(slots), work, self._stream()), entry)
-            self.launches += 3 * int(n_steps) + 2   # (3 n_steps + 3 in all, as rl_learn_dueling_wide)
-        elif entry == "rl_learn_td":
-            tds = (_lib.TdPrio * n)(*[l.td_struct() for l in learners])
-            _lib.check(self.lib.rl_learn_td(self.handle, arr, rings, tds, n, int(n_steps), _ptr(slots), self._stream()), entry)
-        elif entry == "rl_learn_ppo":
-            ppos = (_lib.Ppo * n)(*[l.ppo_struct(gate=gate) for l in learners])
-            _lib.check(self.lib.rl_learn_ppo(self.handle, arr, rings, ppos, n, int(n_steps), _ptr(slots), self._stream()), entry)
-        elif entry == "rl_learn_wide":
-            work = (C.c_void_p * n)(*[l.work.data_ptr() for l in learners])
-            _lib.check(self.lib.rl_learn_wide(self.handle, arr, rings, n, int(n_steps), _ptr(slots), work, self._stream()), entry)
-            self.launches += 2 * int(n_steps) + 2   # (2 n_steps + 3 in all: check, tiles and update per step, target / counters, pack)
-        elif entry == "rl_learn_dueling_wide":
-            if len({l.batch for l in learners}) != 1:
-                raise ValueError("learn(): the rl_learn_dueling_wide learners of a call must share one batch size, got %s" % sorted({l.batch for l in learners}))
-            work = (C.c_void_p * n)(*[l.work.data_ptr() for l in learners])
-            _lib.check(self.lib.rl_learn_dueling_wide(self.handle, arr, rings, n, int(n_steps), _ptr(slots), work, self._stream()), entry)
-            self.launches += 3 * int(n_steps) + 2   # (3 n_steps + 3 in all: check, the two tile passes and the update per step, target / counters, pack)
-        else:
-            _lib.check(getattr(self.lib, entry)(self.handle, arr, rings, n, int(n_steps), _ptr(slots), self._stream()), entry)
+        if spec.one_batch and len({l.batch for l in learners}) != 1:
+            raise ValueError("learn(): the %s learners of a call must share one batch size, got %s" % (spec.name, sorted({l.batch for l in learners})))
+        sides = [(spec.side * n)(*[l.side_struct(spec.side, gate=gate) for l in learners])] if spec.side else []
+        work = [(C.c_void_p * n)(*[l.work.data_ptr() for l in learners])] if spec.narrow else []
+        _lib.check(getattr(self.lib, spec.name)(self.handle, arr, rings, *sides, n, int(n_steps), _ptr(slots), *work, self._stream()), spec.name)
         self._learn_keep = slots   # (the launch reads the table asynchronously)
-        self.launches += 1
+        self.launches += spec.launches(int(n_steps))
 
     def export_learners(self, learners, out=None):
         """The learners' state as ONE flat float32 row on the device (rl_learn_export, one launch, queued on the current stream): learner i's
