@@ -20,6 +20,8 @@
  *   rl_learn_dueling_wide  D3QNAgent.train() on minibatches of up to 2048 rows, 64-row tiles side by side, the batch-wide mean kept
  *   rl_learn_draw_rank this build's own: the minibatch tables of rl_learn / rl_learn_wide / rl_learn_dueling drawn uniformly by the
  *                      rows' content-key rank (one sort per call, one thread per draw)
+ *   rl_learn_prioritized_draw_rank / rl_learn_td_draw_rank  this build's own: the prioritised minibatch tables of PERD3QN.py:157-165 and
+ *                      PERDQN.py:280-304 (stratified) drawn by a prefix sum of the weights in content-key rank order, one search per draw
  *   rl_learn_ppo       PPO.learn(): k_epoch full-batch Adam steps on a rollout of at most 32 rows (rl_learn_rollout draws it)
  *   rl_learn_dueling   D3QNAgent.train(): one minibatch update of the dueling network (MSE, Adam), batch up to 64
  *                      Models/D3QN.py:97-116, 148-165 (schedule and target copy of :118-126: the caller's)
@@ -628,6 +630,63 @@ int rl_learn_prioritized_wide_draw(rl_world* h, const rl_learner* learners, cons
 int rl_learn_prioritized_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners,
                               int n_steps, const int32_t* slots, void* const* work, void* stream);
 
+/* ---- prioritised draws by prefix sum over content-key rank (PERD3QN, PERDQN) --------------------------------------- */
+/* THIS BUILD'S OWN -- the prioritised draws' tables by another sampler.  rl_learn_prioritized_draw / _wide_draw / rl_learn_td_draw race
+ * exponentials: one workgroup per draw, each a pass over the ring, probabilities w_i / sum w up to about size / 2^23, and no way to
+ * stratify.  Here the rows a ring holds are sorted by content key once per call (rl_learn_draw_rank's sort, kernel for kernel), the
+ * weights are summed in that order, and every draw is one binary search: the cost of a call does not depend on n_steps or the batches,
+ * the probabilities are w_i / sum w up to the rounding of a float64 sum, and with one uniform per segment of total / batch the draw is
+ * the reference's stratified Memory.sample() (PERDQN.py:280-304).  rl_learn_prioritized_draw_rank serves RL_PERD3QN learners on rl_prio,
+ * rl_learn_td_draw_rank RL_PERDQN learners on rl_tdprio.  For learner i, size = min(*ring.count, ring.capacity) read on the device:
+ *   prepare   rl_learn_prioritized_draw's (rl_learn_td_draw's) prepare step, unchanged: the slots in [*seen, *count) mod capacity (all
+ *             rows once count - seen >= capacity) get priority = *prio_max (TD: p_new); weight[row] = powf(priority[row], alpha) (TD: no
+ *             weight column, the weight of a row is its stored priority); keys[row] = the content key, rows < size.
+ *   order     host array [n_learners] of device int32 [capacity]: order[i][0 .. size) = the slots ascending by (keys[slot], slot) --
+ *             numpy's lexsort((arange(size), keys[:size])), as rl_learn_draw_rank leaves it.  Entries from `size` on are left alone.
+ *   cum       host array [n_learners] of device float64 [capacity], written for ranks r < size.  With w_r = (double)weight[order[r]]
+ *             where that float is > 0 and w_r = 0 otherwise (a zero, a negative or a NaN weight is never drawn -- the race's rule), in
+ *             IEEE float64, every + one rounded addition:
+ *               local[r] = w_(64 s) + w_(64 s + 1) + ... + w_r, s = r / 64, added left to right starting from 0.0
+ *               tot[s]   = local[min(64 s + 63, size - 1)]
+ *               base[0]  = 0.0, base[s + 1] = base[s] + tot[s]
+ *               cum[r]   = base[r / 64] + local[r],    total = cum[size - 1]
+ *             numpy: np.cumsum over the rows of w padded with zeros to [n_seg][64], a sequential sum of the last column, one add.
+ *             cum is nondecreasing, and a row of weight 0 has cum[r] == cum[r - 1] (rank 0: cum[0] == 0).
+ *   work      host array [n_learners] of device scratch of at least rl_learn_prio_draw_rank_work_bytes(capacity) bytes each, 16-byte
+ *             aligned: rl_learn_draw_rank's two tables of 65,536 counters and one int32 per row, then one float64 per segment of 64
+ *             rows.  It needs no initialisation and holds nothing between calls.
+ *   slots     device int32, the learners' flat [n_steps][batch] tables laid end to end.  Draw d = s * batch + j of learner i:
+ *               r4 = rl_philox(seed, 0, i, (uint32)state[1], SITE, d), SITE = RL_SITE_LEARN_PRIO (PERD3QN) or RL_SITE_LEARN_TD (PERDQN)
+ *                    -- the race draws' own sites: the two samplers are alternatives and never share a call
+ *               x = (((uint64)r4[1] << 32) | r4[0]) >> 11,  u = (double)x * 2^-53          (exact; u in [0, 1))
+ *               stratified == 0:  target = u * total                                      (one multiply)
+ *               stratified != 0:  seg = total / (double)batch,  target = ((double)j + u) * seg   (one divide; one add, then one multiply)
+ *               slots[d] = order[r], r the smallest rank with cum[r] > target; if there is none (rounding gave target >= total), the
+ *               smallest r with cum[r] == total: the last row of positive weight in rank order
+ *             No fused multiply-add anywhere.  A zero-weight row is never the smallest such rank.  total == 0, or a total that is not
+ *             finite: the uniform rank draw slots[d] = order[((uint64)r4[0] * size) >> 32] -- the race's "every weight zero means
+ *             uniform".  size == 0: slot 0 for every draw.  WITH replacement; independent mode is np.random.choice(p = w / sum w)
+ *             (PERD3QN.py:165), stratified mode Memory.sample()'s one random.uniform(a, b) per segment.
+ *   seen      the last launch advances *seen to *ring.count, as the race draws' pick launch does.
+ * batch is in [1, RL_LEARN_PRIORITIZED_WIDE_MAX] (PERD3QN) or [1, 64] (PERDQN); the learners of a call may have different batches.  The
+ * tables feed rl_learn_prioritized, rl_learn_prioritized_wide and rl_learn_td unchanged: their precondition -- a draw has stamped the
+ * fresh rows -- is met, the stamp being the same rule.  All n_steps are drawn from the priorities as they stand at the draw.
+ * RL_LEARN_PRIO_DRAW_RANK_LAUNCHES (8) launches whatever n_steps, the batches and the rings hold, all queued on `stream`: the sort's
+ * five (its key pass also stamps, weighs and counts), the segments' sums (one wave per segment), the bases (one workgroup per learner)
+ * and one thread per draw.  No host read-back, no allocation, integer atomics only: keys, priority, weight, order, cum and slots have
+ * the same bits in every run.  The race draws, rl_learn_draw_rank and every *_supported answer are unchanged by it.
+ * Validated on the host before anything is launched: the race draws' checks -- kind (anything else: RL_E_UNSUPPORTED naming the kind),
+ * the rings' columns (age included), every pointer of rl_prio and alpha > 0 (rl_tdprio: priority, keys, seen), n_learners in
+ * [1, RL_MAX_CAPTURE_BRAINS], n_steps (PERD3QN: [1,65536]; PERDQN: >= 1), the batch range, slots -- and, RL_E_INVALID naming the argument, a
+ * null order, cum or work, a null order[i], cum[i] or work[i], and n_steps times the batches below 2^31 draws. */
+#define RL_LEARN_PRIO_DRAW_RANK_LAUNCHES 8
+/* The bytes of one learner's work buffer for a ring of `capacity` rows (a multiple of 16): hist | start | tmp | segment sums.  0, with
+ * rl_last_error set, for a capacity outside [1, 2^31). */
+size_t rl_learn_prio_draw_rank_work_bytes(long long capacity);
+int rl_learn_prioritized_draw_rank(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners,
+                                   int n_steps, int stratified, int32_t* const* order, double* const* cum, void* const* work,
+                                   int32_t* slots, void* stream);
+
 /* ---- on-policy learning (PPO) ------------------------------------------------------------------------------------ */
 #define RL_PPO_ROLLOUT_MAX 32
 /* What a learning PPO brain needs beside its rl_learner and its rl_replay ring (which must carry `prob`): the hyperparameters of
@@ -718,6 +777,14 @@ int rl_learn_td_supported(int kind);
  * stratified draw's marginal without its variance reduction, by content key, WITH replacement. */
 int rl_learn_td_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
                      int32_t* slots, void* stream);
+/* THIS BUILD'S OWN -- that draw by prefix sum over content-key rank: rl_learn_prioritized_draw_rank (above: order, cum, work, the
+ * formulas, RL_LEARN_PRIO_DRAW_RANK_LAUNCHES launches and rl_learn_prio_draw_rank_work_bytes) on this memory -- fresh rows get p_new, a
+ * row's weight is its stored priority, SITE = RL_SITE_LEARN_TD, batch in [1,64].  stratified != 0 is Memory.sample() itself: the total is
+ * cut into `batch` segments and draw j takes one uniform in segment j -- the deviation rl_learn_td_draw states does not apply; what
+ * remains is that the cumulative sum runs over the rows in content-key order, not in the sum tree's slot order.  stratified == 0: independent
+ * draws with probability p_i / sum p, rl_learn_td_draw's distribution (other rows). */
+int rl_learn_td_draw_rank(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
+                          int stratified, int32_t* const* order, double* const* cum, void* const* work, int32_t* slots, void* stream);
 /* PERDQNAgent.train_model() for n_learners brains in ONE stream-ordered launch, one workgroup per brain.  rl_learner / rl_replay as for
  * rl_learn_dueling; kind = RL_PERDQN: fc.0 153->64, fc.2 64->64, fc.4 64->8, ReLU between, 14,536 parameters in state-dict order.
  *   size gate   size = min(*count, capacity); size <= min_size: no update (the caller passes train_start - 1)

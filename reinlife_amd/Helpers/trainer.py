@@ -132,7 +132,15 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     ((uint64)x_d * size) >> 32, x_d the draw's Philox word -- uniform with replacement and independent of the order the worlds appended
     the rows in, as before, but ANOTHER sampler: other rows, other parameters.  Six launches per draw instead of two, at a cost that does
     not grow with learn_steps x learn_batch (rl_learn_draw visits every key of a ring once per draw).  The prioritised, rollout and
-    PERDQN draws are untouched; learn_ranks="average" needs nothing (draws are rank-local)."""
+    PERDQN draws are untouched; learn_ranks="average" needs nothing (draws are rank-local).
+    learn_draw as a dict by kind, like learn_batch -- keys from "DQN", "D3QN", "PERD3QN", "PERDQN", the only value "rank", every key a kind
+    that has a learner in this run ("PERD3QN" needs learn_prioritized=True, "PERDQN" learn_td_priority=True), checked before a device is
+    touched.  {"DQN": "rank"} / {"D3QN": "rank"} is the string for that kind alone.  {"PERD3QN": "rank"}: the prioritised draw is
+    rl_learn_prioritized_draw_rank -- the same stamp of the fresh rows, the sort above, the weights priority^0.6 summed in rank order in
+    float64 and one binary search per draw: independent draws with probability weight / sum, as the reference's np.random.choice(p=...),
+    at any learn_batch["PERD3QN"], eight launches instead of two at a cost that does not grow with the batch.  {"PERDQN": "rank"}:
+    rl_learn_td_draw_rank, the same STRATIFIED -- the total cut into 64 segments, one uniform per segment: the reference's Memory.sample(),
+    which the race draw cannot do.  Both are other samplers than the race draws: other rows, other parameters."""
     if learn == "device" and (per_agent_api or fused is False):
         raise ValueError("trainer(learn='device') needs the fused path (fused=True, per_agent_api=False): the replay rings are filled "
                          "inside the multi-tick launches")

@@ -155,6 +155,9 @@ class AgentView:
 
 
 class Environment:
+    _DRAW_KINDS = ("DQN", "D3QN", "PERD3QN", "PERDQN")   # the keys of learn_draw as a dict: the brain methods whose draw has a rank variant
+    _DRAW_FAMILY = {"dqn": "DQN", "dueling": "D3QN", "prioritized": "PERD3QN", "td": "PERDQN"}   # ... per family of learn.FAMILIES
+
     def __init__(self, width=30, height=30, brains=None, grid_size=16, max_agents=50, update_interval=500, print_results=True,
                  static_families=True, interactive_results=False, google_colab=False, training=True, save=False,
                  pastel_colors=False, limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None,
@@ -230,13 +233,38 @@ class Environment:
         # learn_draw="rank": the DQN, wide DQN and D3QN learners' minibatches are drawn by content-key rank (rl_learn_draw_rank: one sort
         # per call, one thread per draw) instead of rl_learn_draw's minimum over all keys per draw -- another uniform sampler, so other
         # rows: this build's own, an explicit opt-in.  None: rl_learn_draw, as always.  Checked before a device is touched.
-        if learn_draw not in (None, "rank"):
-            raise ValueError("learn_draw must be None (rl_learn_draw) or 'rank' (uniform draws by content-key rank, rl_learn_draw_rank), got %r" % (learn_draw,))
-        if learn_draw and learn != "device":
-            raise ValueError("learn_draw=%r needs learn='device' (got learn=%r)" % (learn_draw, learn))
-        if learn_draw and not any(getattr(b, "method", None) in self.learn_kinds for b in brains):
-            raise ValueError("learn_draw=%r needs at least one brain that rl_learn, rl_learn_wide or rl_learn_dueling trains: a brain of the "
-                             "learning kinds %r (got %s)" % (learn_draw, self.learn_kinds, ", ".join(str(getattr(b, "method", b)) for b in brains)))
+        # A dict by kind, like learn_batch: {"DQN": "rank"}, {"D3QN": "rank"} (the string, for that kind alone) and, with their opt-ins,
+        # {"PERD3QN": "rank"} -- the prioritised draw by prefix sum over content-key rank, independent draws (rl_learn_prioritized_draw_rank)
+        # -- and {"PERDQN": "rank"} -- the same, stratified: the reference's Memory.sample() (rl_learn_td_draw_rank).  Every key must name
+        # a kind that has a learner in this run.  The string keeps its meaning: the DQN and D3QN families only.
+        self.learn_draw_of = dict.fromkeys(self._DRAW_KINDS)
+        if isinstance(learn_draw, dict):
+            if not learn_draw or any(k not in self._DRAW_KINDS or v != "rank" for k, v in learn_draw.items()):
+                raise ValueError("learn_draw must be None (rl_learn_draw) or 'rank' (uniform draws by content-key rank, rl_learn_draw_rank), or a "
+                                 "dict by kind with the keys %s, the value 'rank' and at least one of them, got %r"
+                                 % (", ".join(repr(k) for k in self._DRAW_KINDS), learn_draw))
+            if learn != "device":
+                raise ValueError("learn_draw=%r needs learn='device' (got learn=%r)" % (learn_draw, learn))
+            for k in learn_draw:
+                opt_in = {"PERD3QN": "learn_prioritized", "PERDQN": "learn_td_priority"}.get(k)
+                if opt_in:   # (the opt-in has made sure of a brain of the kind)
+                    if not getattr(self, opt_in):
+                        raise ValueError("learn_draw names %s: it needs %s=True (its learners are that keyword's)" % (k, opt_in))
+                elif k not in self.learn_kinds or not any(getattr(b, "method", None) == k for b in brains):
+                    raise ValueError("learn_draw names %s: it needs at least one Models.%s brain among the learning kinds %r (got %s)"
+                                     % (k, k, self.learn_kinds, ", ".join(str(getattr(b, "method", b)) for b in brains)))
+            learn_draw = dict(learn_draw)   # (the caller's dict stays the caller's)
+            self.learn_draw_of.update(learn_draw)
+        else:
+            if learn_draw not in (None, "rank"):
+                raise ValueError("learn_draw must be None (rl_learn_draw) or 'rank' (uniform draws by content-key rank, rl_learn_draw_rank), got %r" % (learn_draw,))
+            if learn_draw and learn != "device":
+                raise ValueError("learn_draw=%r needs learn='device' (got learn=%r)" % (learn_draw, learn))
+            if learn_draw and not any(getattr(b, "method", None) in self.learn_kinds for b in brains):
+                raise ValueError("learn_draw=%r needs at least one brain that rl_learn, rl_learn_wide or rl_learn_dueling trains: a brain of the "
+                                 "learning kinds %r (got %s)" % (learn_draw, self.learn_kinds, ", ".join(str(getattr(b, "method", b)) for b in brains)))
+            if learn_draw:
+                self.learn_draw_of.update(DQN="rank", D3QN="rank")
         self.learn_draw = learn_draw
         # learn_ranks="average": the ranks of a process group train independently and merge their learners at the end of every learn_now
         # (periodic parameter averaging; this build's own, the reference has no multi-process training).  Checked before a device is touched.
@@ -760,10 +788,19 @@ class Environment:
             note.append("brains %s as loaded / initialised (their kinds do not learn in this %s)"
                         % (frozen, "run" if any(ks and self._NOTES[name][0] for name, ks in by.items()) else "build"))
         uniform = sorted(k for name, ks in by.items() if not ENTRY[name].draw for k in ks)
-        if self.learn_draw == "rank" and uniform:
-            note.append("the minibatches of brains %s drawn by content-key rank (learn_draw='rank', rl_learn_draw_rank: the ring's rows sorted by "
+        uniform = [k for k in uniform if self.learn_draw_of.get(self.learners[k].spec.method) == "rank"]
+        if uniform:
+            note.append("the minibatches of brains %s drawn by content-key rank (learn_draw=%r, rl_learn_draw_rank: the ring's rows sorted by "
                         "content key, draw d the row at rank (x_d * size) >> 32 -- uniform with replacement, other rows than rl_learn_draw names)"
-                        % uniform)
+                        % (uniform, self.learn_draw))
+        for method, entry, how in (("PERD3QN", "rl_learn_prioritized_draw_rank", "independent draws u_d * total, as np.random.choice's"),
+                                   ("PERDQN", "rl_learn_td_draw_rank", "stratified, draw j at (j + u_j) * total / batch: the reference's Memory.sample(), "
+                                    "not the independent draws the note above states")):
+            ks = [k for k in sorted(self.learners) if self.learners[k].spec.method == method]
+            if ks and self.learn_draw_of.get(method) == "rank":
+                note.append("the minibatches of brains %s drawn by prefix sum over content-key rank (learn_draw=%r, %s: the ring's rows sorted by "
+                            "content key, their weights summed in that order in float64, every draw the smallest rank whose sum exceeds its target -- "
+                            "%s; other rows than the race draw names)" % (ks, self.learn_draw, entry, how))
         if self.learn_ranks:
             note.append("%d rank(s) trained independently on their own rings and averaged params, adam_m and adam_v over the ranks with the "
                         "highest step count after every learning episode (learn_ranks='average': periodic parameter averaging, this build's own)"
@@ -819,13 +856,17 @@ class Environment:
         learn_draw="rank": the draw_slots calls above -- the DQN, wide DQN and D3QN learners' -- are draw_slots_rank calls (rl_learn_draw_rank,
         six launches instead of two: the rings' rows sorted by content key once, every draw an index into that order); the prioritised,
         rollout and PERDQN draws are what they are.
+        learn_draw={"PERD3QN": "rank"}: the prioritised draw is a draw_prioritized_rank call (rl_learn_prioritized_draw_rank, eight launches
+        instead of two: the same stamp, the sort, the weights' cumulative sum in rank order, one search per draw -- independent draws, as
+        np.random.choice's) at any learn_batch["PERD3QN"]; learn_draw={"PERDQN": "rank"}: the PERDQN draw is a draw_td_rank call
+        (rl_learn_td_draw_rank, eight launches, STRATIFIED: the reference's Memory.sample()).  {"DQN": "rank"} / {"D3QN": "rank"}: the string,
+        for that kind alone.  Other rows than the race draws name; without the key every call is what it was.
         learn_ranks="average": all of the above is rank-local and unchanged; the call then ends with the merge of ALL learners over the
         ranks (_merge_learners: one launch to export, ONE all-gather, two launches to merge) -- this build's own, periodic parameter
         averaging: D3QN, PERD3QN and PERDQN learners make one update per call from identical parameters and moments, so the merged
         result is the mean of the ranks' one-step Adam updates; DQN makes learn_steps local steps and PPO k_epoch per rollout in between."""
         self.learn_now_calls += 1
         called = []
-        draw_slots = self.worlds.draw_slots_rank if self.learn_draw == "rank" else self.worlds.draw_slots
         for family, scheduled, draw, per_batch, after in self._SCHEDULE:   # (learn_batch: a family's learners are all wide, or none is)
             ls = [self.learners[k] for k in sorted(self.learners) if self.learners[k].spec.family == family
                   and (not scheduled or last is None or last > self.learners[k].exploration)]
@@ -835,7 +876,8 @@ class Environment:
                 if scheduled and last is not None:
                     for l in ls:
                         l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
-                self.worlds.learn(ls, n, slots=getattr(self.worlds, draw)(ls, n) if draw else draw_slots(ls, n))
+                ranked = "_rank" if self.learn_draw_of.get(self._DRAW_FAMILY.get(family)) == "rank" else ""   # (draw_td_rank: stratified by default)
+                self.worlds.learn(ls, n, slots=getattr(self.worlds, (draw or "draw_slots") + ranked)(ls, n))
                 called += ls
                 if after:
                     after(self, ls, n)
@@ -989,6 +1031,11 @@ def warn_inference_only(frozen=None, kinds=("DQN",), draw=None):
     if frozen is not None:
         # (a line more only where learn_draw was given: every other run's message is what it was)
         drawn = "" if draw is None else "\nlearn_draw=%r draws the DQN / D3QN learners' minibatches by content-key rank (rl_learn_draw_rank)." % (draw,)
+        if isinstance(draw, dict):
+            how = {"DQN": "DQN learners' uniformly by content-key rank (rl_learn_draw_rank)", "D3QN": "D3QN learners' uniformly by content-key rank (rl_learn_draw_rank)",
+                   "PERD3QN": "PERD3QN learners' by priority through a prefix sum over content-key rank, independent draws (rl_learn_prioritized_draw_rank)",
+                   "PERDQN": "PERDQN learners' by priority through a prefix sum over content-key rank, stratified (rl_learn_td_draw_rank)"}
+            drawn = "\nlearn_draw=%r draws the minibatches: the %s." % (draw, "; the ".join(how[k] for k in how if k in draw))
         if tuple(kinds) == ("DQN",):
             warnings.warn("learn='device' trains the DQN brains of this run; brains %s are of kinds rl_learn does not train yet: they stay "
                           "inference only -- brain.learn() is a no-op for them and their weights are NOT updated (D3QN brains learn with "

@@ -93,6 +93,7 @@ LEARN_WIDE_MAX = 2048    # RL_LEARN_WIDE_MAX: the rows of a minibatch at most (r
 LEARN_DUELING_WIDE_MAX = 2048   # RL_LEARN_DUELING_WIDE_MAX: the rows of a minibatch at most (rl_learn_dueling_wide)
 LEARN_PRIORITIZED_WIDE_MAX = 2048   # RL_LEARN_PRIORITIZED_WIDE_MAX: the rows of a minibatch at most (rl_learn_prioritized_wide)
 LEARN_DRAW_RANK_LAUNCHES = 6   # RL_LEARN_DRAW_RANK_LAUNCHES: the launches of one rl_learn_draw_rank call
+LEARN_PRIO_DRAW_RANK_LAUNCHES = 8   # RL_LEARN_PRIO_DRAW_RANK_LAUNCHES: the launches of one rl_learn_prioritized_draw_rank / rl_learn_td_draw_rank call
 PPO_ROLLOUT_MAX = 32    # RL_PPO_ROLLOUT_MAX: the rows of a rollout at most (rl_learn_ppo)
 
 
@@ -151,11 +152,14 @@ ABI = [
     ("rl_learn_prioritized_wide_work_bytes", C.c_size_t, [C.c_int, C.c_int]),
     ("rl_learn_prioritized_wide_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Prio), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_prioritized_wide", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Prio), C.c_int, C.c_int, _P, C.POINTER(_P), _P]),
+    ("rl_learn_prio_draw_rank_work_bytes", C.c_size_t, [C.c_longlong]),
+    ("rl_learn_prioritized_draw_rank", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Prio), C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),
     ("rl_learn_ppo_supported", C.c_int, [C.c_int]),
     ("rl_learn_ppo", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Ppo), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_rollout", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Ppo), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_td_supported", C.c_int, [C.c_int]),
     ("rl_learn_td_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_td_draw_rank", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),
     ("rl_learn_td", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_merge_floats", C.c_int64, [C.c_int]),
     ("rl_learn_export", C.c_int, [_P, C.POINTER(Learner), C.c_int, _P, _P]),

@@ -35,6 +35,9 @@ size_t rl_learn_wide_work_bytes_impl(int);
 int rl_learn_wide_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, const int32_t*, void* const*, hipStream_t);
 size_t rl_learn_draw_rank_work_bytes_impl(long long);
 int rl_learn_draw_rank_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, unsigned long long* const*, int32_t* const*, void* const*, int32_t*, hipStream_t);
+size_t rl_learn_prio_draw_rank_work_bytes_impl(long long);
+int rl_learn_prioritized_draw_rank_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_prio*, int, int, int, int32_t* const*, double* const*, void* const*, int32_t*, hipStream_t);
+int rl_learn_td_draw_rank_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_tdprio*, int, int, int, int32_t* const*, double* const*, void* const*, int32_t*, hipStream_t);
 int rl_learn_dueling_wide_supported_impl(int);
 size_t rl_learn_dueling_wide_work_bytes_impl(int);
 int rl_learn_dueling_wide_launch(rl_world*, const rl_learner*, const rl_replay*, int, int, const int32_t*, void* const*, hipStream_t);
@@ -645,6 +648,41 @@ int rl_learn_prioritized_wide_draw(rl_world* h, const rl_learner* learners, cons
     return rl_learn_prioritized_wide_draw_launch(h, learners, rings, prios, n_learners, n_steps, slots, (hipStream_t)stream);
 }
 
+size_t rl_learn_prio_draw_rank_work_bytes(long long capacity)
+{
+    if (capacity < 1 || capacity > 0x7fffffff) { rl_set_error("rl_learn_prio_draw_rank_work_bytes: capacity must be in [1, 2^31) (got %lld)", capacity); return 0; }
+    return rl_learn_prio_draw_rank_work_bytes_impl(capacity);
+}
+
+// what the two prioritised rank draws ask beyond the race draws' checks: order, cum and work, their entries, and the number of draws
+static int check_draw_rank_buffers(const char* who, const rl_learner* learners, int n_learners, int n_steps, int32_t* const* order, double* const* cum,
+                                   void* const* work)
+{
+    long long draws = 0;
+    for (int i = 0; i < n_learners; ++i) {
+        if (!order[i]) { rl_set_error("%s: order[%d] must not be null", who, i); return RL_E_INVALID; }
+        if (!cum[i]) { rl_set_error("%s: cum[%d] must not be null", who, i); return RL_E_INVALID; }
+        if (!work[i]) { rl_set_error("%s: work[%d] must not be null (rl_learn_prio_draw_rank_work_bytes)", who, i); return RL_E_INVALID; }
+        draws += (long long)n_steps * learners[i].batch;
+    }
+    if (draws > 0x7fffffff) { rl_set_error("%s: n_steps times the learners' batches must stay below 2^31 draws (got %lld)", who, draws); return RL_E_INVALID; }
+    return RL_OK;
+}
+
+int rl_learn_prioritized_draw_rank(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners, int n_steps,
+                                   int stratified, int32_t* const* order, double* const* cum, void* const* work, int32_t* slots, void* stream)
+{
+    const char* who = "rl_learn_prioritized_draw_rank";
+    if (h && !order) { rl_set_error("%s: null order", who); return RL_E_INVALID; }
+    if (h && !cum) { rl_set_error("%s: null cum", who); return RL_E_INVALID; }
+    if (h && !work) { rl_set_error("%s: null work", who); return RL_E_INVALID; }
+    if (int rc = check_prioritized(who, true, h, learners, rings, prios, n_learners, n_steps, slots, RL_LEARN_PRIORITIZED_WIDE_MAX, false,
+                                   "rl_learn_prioritized_wide_supported", who)) return rc;
+    if (int rc = check_draw_rank_buffers(who, learners, n_learners, n_steps, order, cum, work)) return rc;
+    DeviceGuard guard(device_of_pointer(slots));
+    return rl_learn_prioritized_draw_rank_launch(h, learners, rings, prios, n_learners, n_steps, stratified, order, cum, work, slots, (hipStream_t)stream);
+}
+
 int rl_learn_prioritized_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners, int n_steps,
                               const int32_t* slots, void* const* work, void* stream)
 {
@@ -775,6 +813,19 @@ int rl_learn_td_draw(rl_world* h, const rl_learner* learners, const rl_replay* r
     if (int rc = check_td("rl_learn_td_draw", true, h, learners, rings, tds, n_learners, n_steps, slots)) return rc;
     DeviceGuard guard(device_of_pointer(slots));
     return rl_learn_td_draw_launch(h, learners, rings, tds, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+int rl_learn_td_draw_rank(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
+                          int stratified, int32_t* const* order, double* const* cum, void* const* work, int32_t* slots, void* stream)
+{
+    const char* who = "rl_learn_td_draw_rank";
+    if (h && !order) { rl_set_error("%s: null order", who); return RL_E_INVALID; }
+    if (h && !cum) { rl_set_error("%s: null cum", who); return RL_E_INVALID; }
+    if (h && !work) { rl_set_error("%s: null work", who); return RL_E_INVALID; }
+    if (int rc = check_td(who, true, h, learners, rings, tds, n_learners, n_steps, slots)) return rc;
+    if (int rc = check_draw_rank_buffers(who, learners, n_learners, n_steps, order, cum, work)) return rc;
+    DeviceGuard guard(device_of_pointer(slots));
+    return rl_learn_td_draw_rank_launch(h, learners, rings, tds, n_learners, n_steps, stratified, order, cum, work, slots, (hipStream_t)stream);
 }
 
 int rl_learn_td(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,

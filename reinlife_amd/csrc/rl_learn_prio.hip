@@ -57,6 +57,8 @@ struct PrioArgs {
 };
 
 // one wave per ring row: the stamp, weight[row] = priority[row]^alpha (TD: none), keys[row]
+// (rl_learn_rank.hip's k_prank_keys repeats this body and adds the bucket count: a change of the stamp or weight rule goes to both;
+// tests/test_hip_learn_prio_draw_rank.py compares what the two leave, bit for bit)
 template <bool TD>
 __global__ __launch_bounds__(256) void k_prio_prepare(const PrioArgs A)
 {

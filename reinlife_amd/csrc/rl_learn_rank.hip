@@ -26,6 +26,9 @@
 //   k_rank_pick     one thread per draw
 // Six launches whatever n_steps, the batches and the rings hold.  The only atomics are integer adds, and every value the caller sees
 // (keys, order, slots) is independent of the order they arrive in: the same bits in every run.
+//
+// The prioritised memories' draws by the same order (rl_learn_prioritized_draw_rank, rl_learn_td_draw_rank: a cumulative sum of the
+// weights in rank order, one binary search per draw) follow the uniform draw below and reuse its sort kernels as they are.
 #include "rl_learn_dev.h"
 
 namespace {
@@ -172,6 +175,189 @@ __global__ __launch_bounds__(256) void k_rank_pick(const RankArgs A)
     A.slots[B.slots0 + d] = slot;
 }
 
+// ---- prioritised draws by prefix sum over content-key rank (rl_learn_prioritized_draw_rank, rl_learn_td_draw_rank) -------------------
+// THIS BUILD'S OWN sampler beside rl_learn_prio.hip's exponential race (one workgroup per draw, each a pass over the ring).  With `order`
+// fixed, a prioritised draw is a cumulative sum of the weights in rank order and one binary search per draw: the cost of a call does not
+// depend on n_steps x batch, the probabilities are w_i / sum w exactly (up to the sum's rounding), and with one uniform per segment of
+// total / batch it is the reference's stratified Memory.sample() (PERDQN.py:280-304).  The sort is the uniform draw's, kernel for kernel:
+//   k_rank_clear      as above
+//   k_prank_keys      k_rank_keys and rl_learn_prio.hip's k_prio_prepare in one pass: the stamp, weight = priority^alpha (TD: none), key, bucket
+//   k_rank_scan / k_rank_scatter / k_rank_place   as above: order[0 .. size)
+//   k_prank_segments  one wave per segment of kPrankSeg = 64 consecutive ranks: w_r = (double)weight[order[r]] where that is > 0, else 0
+//                     (a NaN too); local[r] = the inclusive left-to-right sum of the segment's w up to r, into cum[r]; the segment's total
+//   k_prank_base      one workgroup per learner: base[s] = the exclusive left-to-right sum of the totals (one thread adds them), then
+//                     cum[r] = base[r / 64] + local[r] -- a fixed association order: the same bits in every run
+//   k_prank_pick      one thread per draw d = s * batch + j: r4 = rl_philox(seed, 0, i, (uint32)state[1], site, d); u = (double)((r4.y : r4.x)
+//                     >> 11) * 2^-53; target = u * total, stratified ((double)j + u) * (total / batch), each one rounded operation after the
+//                     other; the smallest rank r with cum[r] > target (none: the smallest with cum[r] == total); total == 0 or not finite:
+//                     the uniform rank draw order[(r4.x * size) >> 32]; size == 0: slot 0.  Draw 0 advances *seen to *count.
+// Eight launches whatever n_steps, the batches and the rings hold; integer atomics only.
+constexpr int kPrankSeg = 64;
+
+struct PrankBrain {
+    const float *r_state, *r_state_prime, *r_reward;
+    const int8_t* r_action;
+    const uint8_t* r_done;
+    const int32_t* r_age;
+    const unsigned long long* r_count;
+    long long r_capacity;
+    float *priority, *weight;    // (TD: weight is null)
+    const float* wsrc;           // what a draw is proportional to: weight (TD: priority)
+    const float* prio_max;       // (TD: null)
+    unsigned long long* seen;
+    unsigned long long* keys;    // [capacity]
+    const int32_t* order;        // [capacity], written by k_rank_place
+    uint32_t* hist;              // [65536]: the buckets' counters
+    double* cum;                 // [capacity]
+    double* seg;                 // [ceil(capacity / 64)]: the segments' totals, then their bases
+    const long long* state;      // rl_learner.state ([1] = calls made)
+    long long slots0;            // where this learner's [n_steps][batch] table starts in `slots`
+    float p_new;                 // (TD only)
+    float alpha;
+    int batch;
+};
+struct PrankArgs {
+    PrankBrain b[RL_MAX_CAPTURE_BRAINS];
+    int32_t* slots;              // the learners' [n_steps][batch] tables, end to end
+    uint64_t seed;
+    int n_steps;
+    int stratified;
+    int site;                    // RL_SITE_LEARN_PRIO or RL_SITE_LEARN_TD: the race draws' own sites
+};
+static_assert(sizeof(RankArgs) <= 4096, "kernel arguments are passed by value");
+static_assert(sizeof(PrankArgs) <= 4096, "kernel arguments are passed by value");
+
+__device__ inline long long prank_size(const PrankBrain& B)
+{
+    const unsigned long long count = *B.r_count;
+    return count < (unsigned long long)B.r_capacity ? (long long)count : B.r_capacity;
+}
+
+// one wave per ring row: k_prio_prepare's stamp and weight (rl_learn_prio.hip, unchanged), keys[row], and the row counted in its bucket
+template <bool TD>
+__global__ __launch_bounds__(256) void k_prank_keys(const PrankArgs A)
+{
+    const PrankBrain& B = A.b[blockIdx.y];
+    const unsigned long long count = *B.r_count, seen = *B.seen, cap = (unsigned long long)B.r_capacity;
+    const long long size = count < cap ? (long long)count : B.r_capacity;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= size) return;
+    const uint64_t k = learn_row_key(B.r_state, B.r_state_prime, B.r_action, B.r_reward, B.r_done, B.r_age, row, lane);
+    if (lane == 0) {
+        const unsigned long long fresh = count > seen ? count - seen : 0ull;          // rows appended since the last draw
+        const unsigned long long behind = ((unsigned long long)row + cap - seen % cap) % cap;   // slots from seen's to this row's, going round
+        const bool stamp = fresh >= cap || behind < fresh;
+        if (TD) {
+            if (stamp) B.priority[row] = B.p_new;
+        } else {
+            float p;
+            if (stamp) { p = *B.prio_max; B.priority[row] = p; }
+            else p = B.priority[row];
+            B.weight[row] = powf(p, B.alpha);
+        }
+        B.keys[row] = k;
+        atomicAdd(&B.hist[k >> kRankShift], 1u);
+    }
+}
+
+// one wave per segment of 64 consecutive ranks, one lane per rank: the loads side by side, the sum left to right
+__global__ __launch_bounds__(256) void k_prank_segments(const PrankArgs A)
+{
+    const PrankBrain& B = A.b[blockIdx.y];
+    const long long size = prank_size(B);
+    const long long s = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (s * kPrankSeg >= size) return;                    // (the whole wave)
+    const long long r = s * kPrankSeg + lane;
+    double w = 0.0;
+    if (r < size) {
+        const int32_t slot = B.order[r];
+        if (slot >= 0 && slot < size) {                   // (always: order[0 .. size) is a permutation of the slots)
+            const float f = B.wsrc[slot];
+            if (f > 0.0f) w = (double)f;                  // a zero, negative or NaN weight counts as 0
+        }
+    }
+    const int lo = __double2loint(w), hi = __double2hiint(w);
+    double run = 0.0, mine = 0.0;
+#pragma unroll
+    for (int i = 0; i < kPrankSeg; ++i) {
+        run = __dadd_rn(run, __hiloint2double(__builtin_amdgcn_readlane(hi, i), __builtin_amdgcn_readlane(lo, i)));
+        if (lane == i) mine = run;
+    }
+    if (r < size) B.cum[r] = mine;
+    if (lane == 0) B.seg[s] = run;                        // (the ranks past `size` added zeros)
+}
+
+// one workgroup per learner: the segments' totals to their exclusive sums, added by ONE thread in segment order; then cum = base + local
+__global__ __launch_bounds__(256) void k_prank_base(const PrankArgs A)
+{
+    __shared__ double part[256];
+    const PrankBrain& B = A.b[blockIdx.x];
+    const long long size = prank_size(B);
+    const long long n_seg = (size + kPrankSeg - 1) / kPrankSeg;
+    const int tid = threadIdx.x;
+    double run = 0.0;                                     // (thread 0's)
+    for (long long c = 0; c < n_seg; c += 256) {
+        if (c + tid < n_seg) part[tid] = B.seg[c + tid];
+        __syncthreads();
+        if (tid == 0) {
+            const int n = n_seg - c < 256 ? (int)(n_seg - c) : 256;
+            for (int k = 0; k < n; ++k) { const double t = part[k]; part[k] = run; run = __dadd_rn(run, t); }
+        }
+        __syncthreads();
+        if (c + tid < n_seg) B.seg[c + tid] = part[tid];
+        __syncthreads();
+    }
+    for (long long r = tid; r < size; r += 256) B.cum[r] = __dadd_rn(B.seg[r / kPrankSeg], B.cum[r]);
+}
+
+// one thread per draw: a binary search in cum
+__global__ __launch_bounds__(256) void k_prank_pick(const PrankArgs A)
+{
+    const int brain = blockIdx.y;
+    const PrankBrain& B = A.b[brain];
+    const long long d = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (d >= (long long)A.n_steps * B.batch) return;
+    const unsigned long long count = *B.r_count;
+    const long long size = count < (unsigned long long)B.r_capacity ? (long long)count : B.r_capacity;
+    if (d == 0) *B.seen = count;                          // (k_prank_keys, the only reader, is a launch in front of this one)
+    int32_t slot = 0;
+    if (size > 0) {
+        const rl_u4 r4 = rl_philox4x32(A.seed, 0u, (uint32_t)brain, (uint32_t)B.state[1], (uint32_t)A.site, (uint32_t)d);
+        const double total = B.cum[size - 1];
+        long long rank;
+        if (!(total > 0.0) || !(total <= 1.7976931348623157e308)) {               // every weight zero, or a sum that is not finite: uniform
+            rank = (long long)(((uint64_t)r4.x * (uint64_t)size) >> 32);
+        } else {
+            const uint64_t x = (((uint64_t)r4.y << 32) | r4.x) >> 11;
+            const double u = __dmul_rn((double)x, 1.1102230246251565e-16);         // x * 2^-53: exact, in [0, 1)
+            double target;
+            if (A.stratified) {
+                const double seg = __ddiv_rn(total, (double)B.batch);
+                target = __dmul_rn(__dadd_rn((double)(d % B.batch), u), seg);
+            } else {
+                target = __dmul_rn(u, total);
+            }
+            long long lo = 0, hi = size;                  // the smallest rank with cum > target
+            while (lo < hi) {
+                const long long mid = (lo + hi) >> 1;
+                if (B.cum[mid] > target) hi = mid; else lo = mid + 1;
+            }
+            if (lo >= size) {                             // rounding gave target >= total: the smallest rank with cum == total
+                lo = 0; hi = size - 1;
+                while (lo < hi) {
+                    const long long mid = (lo + hi) >> 1;
+                    if (B.cum[mid] >= total) hi = mid; else lo = mid + 1;
+                }
+            }
+            rank = lo;
+        }
+        slot = B.order[rank];
+    }
+    A.slots[B.slots0 + d] = slot;
+}
+
 }  // namespace
 
 size_t rl_learn_draw_rank_work_bytes_impl(long long capacity)
@@ -208,4 +394,69 @@ int rl_learn_draw_rank_launch(rl_world* h, const rl_learner* learners, const rl_
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { rl_set_error("rl_learn_draw_rank: kernel launch failed: %s", hipGetErrorString(e)); return RL_E_LAUNCH; }
     return RL_OK;
+}
+
+size_t rl_learn_prio_draw_rank_work_bytes_impl(long long capacity)
+{
+    const size_t n_seg = ((size_t)capacity + kPrankSeg - 1) / kPrankSeg;
+    return rl_learn_draw_rank_work_bytes_impl(capacity) + ((n_seg * sizeof(double) + 15) & ~(size_t)15);
+}
+
+// prios (PERD3QN) or tds (PERDQN), the other null: hist | start | tmp | the segments' sums in work[i]
+static int prank_launch(const char* who, rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, const rl_tdprio* tds,
+                        int n_learners, int n_steps, int stratified, int32_t* const* order, double* const* cum, void* const* work, int32_t* slots,
+                        hipStream_t stream)
+{
+    RankArgs s{};       // the sort's view of the same buffers
+    PrankArgs a{};
+    long long max_cap = 1, slots0 = 0;
+    int max_batch = 1;
+    for (int i = 0; i < n_learners; ++i) {
+        const rl_replay& r = rings[i];
+        RankBrain& sb = s.b[i];
+        PrankBrain& b = a.b[i];
+        b.r_state = r.state; b.r_state_prime = r.state_prime; b.r_reward = r.reward; b.r_action = r.action; b.r_done = r.done; b.r_age = r.age;
+        b.r_count = r.count; b.r_capacity = r.capacity;
+        if (tds) { b.priority = tds[i].priority; b.wsrc = tds[i].priority; b.keys = tds[i].keys; b.seen = tds[i].seen; b.p_new = tds[i].p_new; }
+        else { const rl_prio& p = prios[i]; b.priority = p.priority; b.weight = p.weight; b.wsrc = p.weight; b.keys = p.keys; b.prio_max = p.prio_max; b.seen = p.seen; b.alpha = p.alpha; }
+        sb.r_count = r.count; sb.r_capacity = r.capacity; sb.keys = b.keys; sb.order = order[i];
+        sb.hist = (uint32_t*)work[i]; sb.start = sb.hist + kRankBuckets; sb.tmp = (int32_t*)(sb.start + kRankBuckets);
+        b.order = order[i]; b.hist = sb.hist; b.cum = cum[i];
+        b.seg = (double*)((char*)work[i] + rl_learn_draw_rank_work_bytes_impl(r.capacity));
+        b.state = (const long long*)learners[i].state; b.batch = learners[i].batch; b.slots0 = slots0;
+        slots0 += (long long)n_steps * b.batch;
+        max_cap = r.capacity > max_cap ? r.capacity : max_cap;
+        max_batch = b.batch > max_batch ? b.batch : max_batch;
+    }
+    a.slots = slots; a.seed = h->cfg.seed; a.n_steps = n_steps; a.stratified = stratified ? 1 : 0;
+    a.site = tds ? RL_SITE_LEARN_TD : RL_SITE_LEARN_PRIO;
+    const unsigned row_blocks = (unsigned)((max_cap + 255) / 256);
+    const unsigned seg_blocks = (unsigned)(((max_cap + kPrankSeg - 1) / kPrankSeg + 3) / 4);
+    const unsigned draw_blocks = (unsigned)(((long long)n_steps * max_batch + 255) / 256);
+    hipLaunchKernelGGL(k_rank_clear, dim3(kRankBuckets / 4 / 256, n_learners), dim3(256), 0, stream, s);
+    if (tds) hipLaunchKernelGGL(k_prank_keys<true>, dim3((unsigned)((max_cap + 3) / 4), n_learners), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(k_prank_keys<false>, dim3((unsigned)((max_cap + 3) / 4), n_learners), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(k_rank_scan, dim3(n_learners), dim3(kScanBlock), 0, stream, s);
+    hipLaunchKernelGGL(k_rank_scatter, dim3(row_blocks, n_learners), dim3(256), 0, stream, s);
+    hipLaunchKernelGGL(k_rank_place, dim3(row_blocks, n_learners), dim3(256), 0, stream, s);
+    hipLaunchKernelGGL(k_prank_segments, dim3(seg_blocks, n_learners), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(k_prank_base, dim3(n_learners), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(k_prank_pick, dim3(draw_blocks, n_learners), dim3(256), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { rl_set_error("%s: kernel launch failed: %s", who, hipGetErrorString(e)); return RL_E_LAUNCH; }
+    return RL_OK;
+}
+
+int rl_learn_prioritized_draw_rank_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners,
+                                          int n_steps, int stratified, int32_t* const* order, double* const* cum, void* const* work,
+                                          int32_t* slots, hipStream_t stream)
+{
+    return prank_launch("rl_learn_prioritized_draw_rank", h, learners, rings, prios, nullptr, n_learners, n_steps, stratified, order, cum, work, slots, stream);
+}
+
+int rl_learn_td_draw_rank_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners,
+                                 int n_steps, int stratified, int32_t* const* order, double* const* cum, void* const* work, int32_t* slots,
+                                 hipStream_t stream)
+{
+    return prank_launch("rl_learn_td_draw_rank", h, learners, rings, nullptr, tds, n_learners, n_steps, stratified, order, cum, work, slots, stream);
 }

@@ -204,6 +204,7 @@ class DeviceLearner:
         # a wide entry's scratch (header, the tiles' partial gradients and sums, rl_learn_dueling_wide's per-row stash); needs no initialisation
         self.work = torch.empty(int(getattr(lib, spec.work_bytes)(self.kind, self.batch)), dtype=torch.uint8, device=self.device) if spec.narrow else None
         self.rank_order = self.rank_work = None   # DeviceWorlds.draw_slots_rank: the ring's slots in key order, and rl_learn_draw_rank's scratch
+        self.rank_cum = None      # DeviceWorlds.draw_prioritized_rank / draw_td_rank: the weights' cumulative sum in key order (float64)
         self.loss = None          # optional device float32 [n_steps]
         self.grad = None          # optional device float32 [n_steps, n_params] (tests, diagnostics)
 

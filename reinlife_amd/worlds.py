@@ -501,6 +501,57 @@ class DeviceWorlds:
         draws are independent).  Device int32 [len(learners), n_steps, batch], queued on the current stream."""
         return self._draw_side("draw_td", learners, n_steps, _lib.TdPrio, "a PERDQN one (DeviceLearner(..., td_priority=True))")
 
+    def draw_prioritized_rank(self, learners, n_steps, stratified=False):
+        """draw_prioritized() by another sampler (rl_learn_prioritized_draw_rank, this build's own): the same stamp of the rows appended
+        since the last draw, then every ring's rows sorted by content key once, their weights priority^alpha summed in that order in
+        float64 (segments of 64, a fixed association order), and draw d the row at the smallest rank whose cumulative sum exceeds
+        u_d * total -- probability weight / sum exactly, with replacement, the same rows whatever slots they sit in, at a cost that does
+        not depend on n_steps or the batch (draw_prioritized makes a pass over the ring per draw).  stratified=True cuts the total into
+        `batch` segments and takes draw j inside segment j.  Other rows than draw_prioritized names.  Narrow and wide prioritised
+        learners alike (batch 1 .. 2048; one batch per call, the table being one tensor -- the C entry allows a batch per learner).
+        Device int32 [len(learners), n_steps, batch], queued on the current stream.  Keeps
+        learner.rank_order, learner.rank_cum (float64, [0, size) defined) and learner.rank_work on the learners, allocated once per ring size."""
+        return self._draw_side_rank("draw_prioritized_rank", "rl_learn_prioritized_draw_rank", learners, n_steps, stratified, _lib.Prio,
+                                    "a prioritised one (DeviceLearner(..., prioritized=True))")
+
+    def draw_td_rank(self, learners, n_steps, stratified=True):
+        """draw_td() by that sampler (rl_learn_td_draw_rank): fresh rows get learner.p_new, a row's weight is its stored priority.
+        stratified=True (the default) is the reference's Memory.sample(): the total is cut into `batch` segments and draw j takes one
+        uniform in segment j -- over the rows in content-key order, so the same rows whatever slots they sit in.  Device int32
+        [len(learners), n_steps, batch], queued on the current stream."""
+        return self._draw_side_rank("draw_td_rank", "rl_learn_td_draw_rank", learners, n_steps, stratified, _lib.TdPrio,
+                                    "a PERDQN one (DeviceLearner(..., td_priority=True))")
+
+    def _draw_side_rank(self, who, draw, learners, n_steps, stratified, side, one_of):
+        """draw_prioritized_rank / draw_td_rank: the C entry `draw`, fed the learners' side structs and their order / cum / work buffers.
+        The learners of a call must share one batch -- deliberately, as for every draw_* here: the table comes back as ONE tensor
+        [n, n_steps, batch], which DeviceWorlds.learn takes as it is (Environment.learn_now makes one call per batch size).  The C entry
+        itself lays the learners' tables end to end and allows a batch per learner."""
+        n = len(learners)
+        if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
+            raise ValueError("%s(): 1 to %d learners per call (got %d)" % (who, _lib.MAX_CAPTURE_BRAINS, n))
+        if len({l.batch for l in learners}) != 1:
+            raise ValueError("%s(): the learners of a call must share one batch size" % who)
+        if any(l.spec.side is not side for l in learners):
+            raise ValueError("%s(): every learner must be %s" % (who, one_of))
+        for l in learners:
+            capacity = int(l.ring["state"].shape[0])
+            if getattr(l, "rank_cum", None) is None or l.rank_cum.numel() != capacity:
+                l.rank_order = torch.zeros(capacity, dtype=torch.int32, device=self.device)
+                l.rank_cum = torch.zeros(capacity, dtype=torch.float64, device=self.device)
+                l.rank_work = torch.empty(int(self.lib.rl_learn_prio_draw_rank_work_bytes(capacity)), dtype=torch.uint8, device=self.device)
+        arr = (_lib.Learner * n)(*[l.struct() for l in learners])
+        rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
+        sides = (side * n)(*[l.side_struct(side) for l in learners])
+        order = (C.c_void_p * n)(*[l.rank_order.data_ptr() for l in learners])
+        cum = (C.c_void_p * n)(*[l.rank_cum.data_ptr() for l in learners])
+        work = (C.c_void_p * n)(*[l.rank_work.data_ptr() for l in learners])
+        slots = torch.zeros((n, int(n_steps), int(learners[0].batch)), dtype=torch.int32, device=self.device)
+        _lib.check(getattr(self.lib, draw)(self.handle, arr, rings, sides, n, int(n_steps), int(bool(stratified)), order, cum, work, _ptr(slots),
+                                           self._stream()), draw)
+        self.launches += _lib.LEARN_PRIO_DRAW_RANK_LAUNCHES
+        return slots
+
     def _draw_side(self, who, learners, n_steps, side, one_of):
         """draw_prioritized / draw_rollout / draw_td: the draw entry of the learners' own (Entry.draw), fed their side structs of type `side`."""
         n = len(learners)
