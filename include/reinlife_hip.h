@@ -22,6 +22,8 @@
  *                      rows' content-key rank (one sort per call, one thread per draw)
  *   rl_learn_prioritized_draw_rank / rl_learn_td_draw_rank  this build's own: the prioritised minibatch tables of PERD3QN.py:157-165 and
  *                      PERDQN.py:280-304 (stratified) drawn by a prefix sum of the weights in content-key rank order, one search per draw
+ *   rl_learn_td_stamp  this build's own: the rows appended since the last draw get the TD-error priority PERDQN.py:113-128 spells out
+ *                      and does not compute (a forward pass of both networks per fresh row)
  *   rl_learn_ppo       PPO.learn(): k_epoch full-batch Adam steps on a rollout of at most 32 rows (rl_learn_rollout draws it)
  *   rl_learn_dueling   D3QNAgent.train(): one minibatch update of the dueling network (MSE, Adam), batch up to 64
  *                      Models/D3QN.py:97-116, 148-165 (schedule and target copy of :118-126: the caller's)
@@ -785,6 +787,27 @@ int rl_learn_td_draw(rl_world* h, const rl_learner* learners, const rl_replay* r
  * draws with probability p_i / sum p, rl_learn_td_draw's distribution (other rows). */
 int rl_learn_td_draw_rank(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
                           int stratified, int32_t* const* order, double* const* cum, void* const* work, int32_t* slots, void* stream);
+/* THIS BUILD'S OWN -- the TD error at append.  PERDQNAgent.append_sample (PERDQN.py:113-128) means to store a row with
+ * (|Q(s)[a] - (r + (1 - done) gamma max_a Q_target(s'))| + e) ** a and stores it with (0 + e) ** a, because old_val (:119) is a view of
+ * the tensor :121-124 overwrite (point 1 above).  The draws reproduce that constant (p_new); this call, queued IN FRONT of a draw, gives
+ * the rows of the draw's window the priority the code spells out -- a departure from PERDQN.py:119-126 on purpose, opt-in, and
+ * with a schedule of our own: the error is taken with params / target AS OF THIS CALL, not as of the tick that stored the row.
+ *   window     the slots of [*seen, *ring.count) mod capacity, or all min(count, capacity) rows once count - seen >= capacity: exactly
+ *              the rows the following draw would have stamped with p_new
+ *   launch 1   one workgroup per (learner, 64 window rows), workgroups beyond the window return at once: `target` on the s' rows and
+ *              max_a, `params` on the s rows, priority[slot] = powf(fabsf(q[a] - (r + mask * (gamma * max))) + prio_e, prio_a).  Every
+ *              dot product is rl_learn_td's chain (from the bias, fmaf with k ascending): a stamped priority is, BIT FOR BIT, what
+ *              rl_learn_td would write for that row from the same params and target.  Reads seen and count; writes priority of window
+ *              rows and nothing else; no float atomics; no workgroup waits for another
+ *   launch 2   one thread per learner: *seen = *ring.count (launch 1 is seen's reader)
+ * A following rl_learn_td_draw / rl_learn_td_draw_rank, unchanged, finds an empty window, stamps nothing and draws by the priorities it
+ * finds.  keys, beta, p_new, batch and min_size are not read; the stamp also runs below rl_learn_td's size gate.  No allocation, no host
+ * round trip.  RL_E_INVALID naming the argument for: a null handle, learners, rings or tds; n_learners outside
+ * [1, RL_MAX_CAPTURE_BRAINS]; null params, target, priority or seen; a null ring column among state / state_prime / action / reward /
+ * done / count; capacity outside [1, 2^31); prio_a <= 0.  A kind that is not RL_PERDQN: RL_E_UNSUPPORTED naming the kind. */
+#define RL_LEARN_TD_STAMP_LAUNCHES 2
+int rl_learn_td_stamp(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds,
+                      int n_learners, void* stream);
 /* PERDQNAgent.train_model() for n_learners brains in ONE stream-ordered launch, one workgroup per brain.  rl_learner / rl_replay as for
  * rl_learn_dueling; kind = RL_PERDQN: fc.0 153->64, fc.2 64->64, fc.4 64->8, ReLU between, 14,536 parameters in state-dict order.
  *   size gate   size = min(*count, capacity); size <= min_size: no update (the caller passes train_start - 1)

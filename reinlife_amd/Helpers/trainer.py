@@ -20,7 +20,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
             limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None, seed=0, rng=None, per_agent_api=False,
             fused=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
             learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
-            learn_td_priority=None, learn_ranks=None, learn_batch=None, learn_draw=None):
+            learn_td_priority=None, learn_td_stamp=None, learn_ranks=None, learn_batch=None, learn_draw=None):
     """Extra keyword-only arguments: n_worlds / device / seed / rng / synthetic_agents / refill_below (Environment); per_agent_api=True makes the reference's literal
     per-agent get_action / learn calls; fused (default: True for rng="philox" without per_agent_api) runs the loop through
     Environment.run -- whole chunks of ticks per launch, ending where the Tracker closes an interval -- instead of three launches
@@ -91,6 +91,15 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     probability p_i / sum p, by content key, with replacement; the schedule is per `learn_every` episodes, so brain.epsilon decays
     once per update made, not once per agent trigger (pass a smaller explore_step for the reference's rate in wall-clock terms).  Until a
     ring first holds train_start rows each learning call reads its count back (a synchronisation); afterwards none does.
+    learn_td_stamp (default None: every run is launch for launch and bit for bit what it was; "error" needs learn_td_priority=True, and
+    with it learn="device" and a Models.PERDQN; anything else is a ValueError before a device is touched): THIS BUILD'S OWN, a departure
+    from the first of those three quirks on purpose.  Every learning call then queues one rl_learn_td_stamp (two launches) in front of
+    the PERDQN draw -- the race draw and learn_draw={"PERDQN": "rank"} alike: every row appended since the last draw gets
+    (|Q(s)[a] - (r + (1 - done) gamma max_a Q_target(s'))| + 0.01) ** 0.6, the priority append_sample's code spells out, from a forward
+    pass of both networks over the fresh rows, and the draw that follows finds no fresh row and draws by these priorities.  The error
+    is taken with the parameters AS OF THE LEARNING CALL, not as of the tick that stored the row (the reference's append_sample runs per
+    stored row, between its per-agent train_model() calls): the schedule is ours.  Count read-back, epsilon's decay, the other
+    families and learn_ranks="average" are untouched; priorities stay rank-local.
     learn_ranks (default None: learning needs a single rank, as before; "average" needs learn="device", anything else is a ValueError
     before a device is touched): training on several ranks, THIS BUILD'S OWN -- the reference has no multi-process training.  Every
     rank trains its learners on its own rings exactly as above (draws, calls, priorities and PPO windows are rank-local and unchanged).
@@ -151,7 +160,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
                       device=device, seed=seed, rng=rng, synthetic_agents=synthetic_agents, refill_below=refill_below, dist=dist,
                       world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps, learn_kinds=learn_kinds,
                       learn_prioritized=learn_prioritized, learn_rollout=learn_rollout, rollout_steps=rollout_steps,
-                      learn_td_priority=learn_td_priority, learn_ranks=learn_ranks, learn_batch=learn_batch, learn_draw=learn_draw)
+                      learn_td_priority=learn_td_priority, learn_td_stamp=learn_td_stamp, learn_ranks=learn_ranks, learn_batch=learn_batch, learn_draw=learn_draw)
     env.reset()
     if fused is None:
         fused = env.rng == "philox" and not per_agent_api

@@ -163,7 +163,7 @@ class Environment:
                  pastel_colors=False, limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None,
                  seed=0, rng=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
                  learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
-                 learn_td_priority=None, learn_ranks=None, learn_batch=None, learn_draw=None):
+                 learn_td_priority=None, learn_td_stamp=None, learn_ranks=None, learn_batch=None, learn_draw=None):
         if not brains:
             raise ValueError("Environment needs a non-empty list of brains")
         if learn not in (None, "device"):
@@ -191,6 +191,16 @@ class Environment:
         # learn_td_priority=True: every PERDQN brain trains through rl_learn_td on the reference's prioritised memory with importance
         # weights (PERDQN.py: train_model, Memory).  A keyword of its own, like learn_prioritized.  Checked before a device is touched.
         self._opt_in("td_priority", learn_td_priority, learn, brains)
+        # learn_td_stamp="error": every learning call queues one rl_learn_td_stamp in front of the PERDQN draw -- the rows appended since
+        # the last draw get the TD-error priority append_sample spells out, not its constant (this build's own; PERDQN.py:113-128).  It
+        # rides on learn_td_priority=True, which has made sure of learn="device" and a Models.PERDQN.  Checked before a device is touched.
+        if learn_td_stamp not in (None, "error"):
+            raise ValueError("learn_td_stamp must be None (fresh PERDQN rows get the reference's constant (0 + e) ** a) or 'error' (they get "
+                             "their TD error's priority, rl_learn_td_stamp), got %r" % (learn_td_stamp,))
+        if learn_td_stamp and not self.learn_td_priority:
+            raise ValueError("learn_td_stamp=%r needs learn_td_priority=True (it stamps the PERDQN learners' memories; with it learn='device' "
+                             "and at least one Models.PERDQN)" % (learn_td_stamp,))
+        self.learn_td_stamp = learn_td_stamp
         # learn_batch=B: every DQN learner trains through rl_learn_wide on minibatches of B rows (1 .. 2048) in 32-row tiles side by side
         # (this build's own: the reference's minibatch is 32, DQN.py:16).  None: rl_learn, as always.  Checked before a device is touched.
         # A dict by kind, like learn_steps: {"DQN": B}, {"D3QN": B} or both -- "D3QN": every D3QN learner trains through rl_learn_dueling_wide
@@ -435,6 +445,8 @@ class Environment:
             if l.spec.narrow:   # (the other entry points' batches come from the brains' classes: the signatures of runs without learn_batch stay what they were)
                 sig += [l.batch]
         sig += [self.learn_every, self.learn_steps_of["DQN"], self.learn_steps_of["D3QN"], self.learn_steps_of["PERDQN"], self.rollout_steps]
+        if self.learn_td_stamp:   # (appended, and only when given: every other run's signature stays what it was)
+            sig += [1]
         check_learner_signature(sig, self.dist, device=self.worlds.device)
         flat = torch.cat([l.params for l in ls])
         broadcast_from_rank0(flat, self.dist)
@@ -734,6 +746,8 @@ class Environment:
             settings["Learn batch"] = self.learn_batch
         if self.learn_draw is not None:    # (likewise)
             settings["Learn draw"] = self.learn_draw
+        if self.learn_td_stamp is not None:   # (likewise)
+            settings["Learn td stamp"] = self.learn_td_stamp
         if self.static_families:
             agents = [SavedAgent(g, b) for g, b in enumerate(self.brains)]
         else:  # the brains the best agents descend from (inference-time copies share their weights)
@@ -801,6 +815,11 @@ class Environment:
                 note.append("the minibatches of brains %s drawn by prefix sum over content-key rank (learn_draw=%r, %s: the ring's rows sorted by "
                             "content key, their weights summed in that order in float64, every draw the smallest rank whose sum exceeds its target -- "
                             "%s; other rows than the race draw names)" % (ks, self.learn_draw, entry, how))
+        if self.learn_td_stamp:   # (a clause more only where the keyword was given: every other run's note is what it was)
+            note.append("the new rows of brains %s get (|Q(s)[a] - (r + (1 - done) gamma max_a Q_target(s'))| + 0.01) ** 0.6, their TD error's "
+                        "priority from the parameters as of the learning call that first draws them, not the one priority the note above states "
+                        "(learn_td_stamp=%r, rl_learn_td_stamp: this build's own, a departure from PERDQN.py:113-128 on purpose)"
+                        % ([k for k in sorted(self.learners) if self.learners[k].spec.family == "td"], self.learn_td_stamp))
         if self.learn_ranks:
             note.append("%d rank(s) trained independently on their own rings and averaged params, adam_m and adam_v over the ranks with the "
                         "highest step count after every learning episode (learn_ranks='average': periodic parameter averaging, this build's own)"
@@ -861,6 +880,9 @@ class Environment:
         np.random.choice's) at any learn_batch["PERD3QN"]; learn_draw={"PERDQN": "rank"}: the PERDQN draw is a draw_td_rank call
         (rl_learn_td_draw_rank, eight launches, STRATIFIED: the reference's Memory.sample()).  {"DQN": "rank"} / {"D3QN": "rank"}: the string,
         for that kind alone.  Other rows than the race draws name; without the key every call is what it was.
+        learn_td_stamp="error": one DeviceWorlds.stamp_td (rl_learn_td_stamp, two launches) is queued in front of the PERDQN draw, the race
+        draw and the rank draw alike: the rows appended since the last draw get their TD error's priority from the parameters as they
+        stand at this call, the draw stamps nothing.  Without the key every call is what it was.
         learn_ranks="average": all of the above is rank-local and unchanged; the call then ends with the merge of ALL learners over the
         ranks (_merge_learners: one launch to export, ONE all-gather, two launches to merge) -- this build's own, periodic parameter
         averaging: D3QN, PERD3QN and PERDQN learners make one update per call from identical parameters and moments, so the merged
@@ -877,6 +899,8 @@ class Environment:
                     for l in ls:
                         l.sync_target = last // l.soft_update_freq > max(last - self.learn_every, 0) // l.soft_update_freq
                 ranked = "_rank" if self.learn_draw_of.get(self._DRAW_FAMILY.get(family)) == "rank" else ""   # (draw_td_rank: stratified by default)
+                if family == "td" and self.learn_td_stamp:   # (the draw behind it, whichever it is, then finds no fresh row)
+                    self.worlds.stamp_td(ls)
                 self.worlds.learn(ls, n, slots=getattr(self.worlds, (draw or "draw_slots") + ranked)(ls, n))
                 called += ls
                 if after:

@@ -94,7 +94,8 @@ LEARN_DUELING_WIDE_MAX = 2048   # RL_LEARN_DUELING_WIDE_MAX: the rows of a minib
 LEARN_PRIORITIZED_WIDE_MAX = 2048   # RL_LEARN_PRIORITIZED_WIDE_MAX: the rows of a minibatch at most (rl_learn_prioritized_wide)
 LEARN_DRAW_RANK_LAUNCHES = 6   # RL_LEARN_DRAW_RANK_LAUNCHES: the launches of one rl_learn_draw_rank call
 LEARN_PRIO_DRAW_RANK_LAUNCHES = 8   # RL_LEARN_PRIO_DRAW_RANK_LAUNCHES: the launches of one rl_learn_prioritized_draw_rank / rl_learn_td_draw_rank call
-PPO_ROLLOUT_MAX = 32    # RL_PPO_ROLLOUT_MAX: the rows of a rollout at most (rl_learn_ppo)
+LEARN_TD_STAMP_LAUNCHES = 2   # RL_LEARN_TD_STAMP_LAUNCHES: the launches of one rl_learn_td_stamp call
+PPO_ROLLOUT_MAX = 32   # RL_PPO_ROLLOUT_MAX: the rows of a rollout at most (rl_learn_ppo)
 
 
 class Brain(C.Structure):
@@ -160,6 +161,7 @@ ABI = [
     ("rl_learn_td_supported", C.c_int, [C.c_int]),
     ("rl_learn_td_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_td_draw_rank", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),
+    ("rl_learn_td_stamp", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, _P]),
     ("rl_learn_td", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_merge_floats", C.c_int64, [C.c_int]),
     ("rl_learn_export", C.c_int, [_P, C.POINTER(Learner), C.c_int, _P, _P]),

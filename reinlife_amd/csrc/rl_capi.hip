@@ -52,6 +52,7 @@ int rl_learn_prioritized_wide_draw_launch(rl_world*, const rl_learner*, const rl
 int rl_learn_td_supported_impl(int);
 int rl_learn_td_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_tdprio*, int, int, const int32_t*, hipStream_t);
 int rl_learn_td_draw_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_tdprio*, int, int, int32_t*, hipStream_t);
+int rl_learn_td_stamp_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_tdprio*, int, hipStream_t);
 int rl_learn_ppo_supported_impl(int);
 int rl_learn_ppo_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, const int32_t*, hipStream_t);
 int rl_learn_rollout_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, int32_t*, hipStream_t);
@@ -834,6 +835,35 @@ int rl_learn_td(rl_world* h, const rl_learner* learners, const rl_replay* rings,
     if (int rc = check_td("rl_learn_td", false, h, learners, rings, tds, n_learners, n_steps, slots)) return rc;
     DeviceGuard guard(device_of_pointer(learners[0].params));
     return rl_learn_td_launch(h, learners, rings, tds, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+// rl_learn_td_stamp reads neither batch, min_size, keys, beta nor p_new: its own check, argument by argument
+int rl_learn_td_stamp(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, void* stream)
+{
+    const char* who = "rl_learn_td_stamp";
+    if (!h) { rl_set_error("%s: null handle", who); return RL_E_INVALID; }
+    if (!learners) { rl_set_error("%s: null learners", who); return RL_E_INVALID; }
+    if (!rings) { rl_set_error("%s: null rings", who); return RL_E_INVALID; }
+    if (!tds) { rl_set_error("%s: null tds", who); return RL_E_INVALID; }
+    if (n_learners < 1 || n_learners > RL_MAX_CAPTURE_BRAINS) { rl_set_error("%s: n_learners must be in [1,%d] (got %d)", who, RL_MAX_CAPTURE_BRAINS, n_learners); return RL_E_INVALID; }
+    for (int i = 0; i < n_learners; ++i) {
+        const rl_learner& l = learners[i];
+        const rl_replay& r = rings[i];
+        const rl_tdprio& p = tds[i];
+        if (!rl_learn_td_supported_impl(l.kind)) { rl_set_error("%s: learner %d has brain kind %d; this entry point stamps RL_PERDQN (4) memories only (rl_learn_td_supported)", who, i, l.kind); return RL_E_UNSUPPORTED; }
+        if (!l.params) { rl_set_error("%s: learner %d: params must not be null", who, i); return RL_E_INVALID; }
+        if (!l.target) { rl_set_error("%s: learner %d: target must not be null", who, i); return RL_E_INVALID; }
+        const void* cols[6] = {r.state, r.state_prime, r.action, r.reward, r.done, r.count};
+        static const char* const names[6] = {"state", "state_prime", "action", "reward", "done", "count"};
+        for (int c = 0; c < 6; ++c)
+            if (!cols[c]) { rl_set_error("%s: replay %d: %s must not be null", who, i, names[c]); return RL_E_INVALID; }
+        if (r.capacity < 1 || r.capacity > 0x7fffffff) { rl_set_error("%s: replay %d: capacity must be in [1, 2^31) (got %lld)", who, i, (long long)r.capacity); return RL_E_INVALID; }
+        if (!p.priority) { rl_set_error("%s: td %d: priority must not be null", who, i); return RL_E_INVALID; }
+        if (!p.seen) { rl_set_error("%s: td %d: seen must not be null", who, i); return RL_E_INVALID; }
+        if (!(p.prio_a > 0.0f)) { rl_set_error("%s: td %d: prio_a must be > 0 (got %g)", who, i, (double)p.prio_a); return RL_E_INVALID; }
+    }
+    DeviceGuard guard(device_of_pointer(tds[0].priority));
+    return rl_learn_td_stamp_launch(h, learners, rings, tds, n_learners, (hipStream_t)stream);
 }
 
 int64_t rl_learn_merge_floats(int kind) { return rl_learn_merge_floats_impl(kind); }

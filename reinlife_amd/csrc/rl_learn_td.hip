@@ -388,7 +388,125 @@ __global__ __launch_bounds__(kTBlock) void k_learn_perdqn(const TdArgs A)
     td_pack(B.params, B.packed, sc, un, tid);
 }
 
+// ---- rl_learn_td_stamp: THIS BUILD'S OWN -- the TD-error priority of the rows appended since the last draw --------------------------
+// PERDQN.py:113-128 (append_sample) spells out (|Q(s)[a] - (r + (1 - done) gamma max_a Q_target(s'))| + e) ** a for a row it stores and
+// computes (0 + e) ** a (quirk 1 above).  k_td_stamp computes what the code spells out, for the draws' window -- the slots of
+// [*seen, *count) mod capacity, all rows once count - seen >= capacity -- and k_td_stamp_seen, the launch behind it, closes the window
+// (*seen = *count), so that a following draw, unchanged code, stamps nothing.
+//
+// One 512-thread workgroup per (learner, 64 window rows): the steps of k_learn_perdqn between its row scalars and its priority write,
+// made by the SAME functions (td_stage_rows, td_network) on the same LDS map without D1 / D2 -- a stamped priority is, bit for bit,
+// what k_learn_perdqn writes for that row from the same parameters.  77,568 bytes of dynamic LDS: two workgroups share a CU.  The
+// weights come from L1 / L2 by td_forward's strided reads, as in the learner (DESIGN.md 5.29 on what that costs here).
+// Reads seen and count, writes priority[slot] of window rows and nothing else; no atomics; no workgroup waits for another.
+struct StampBrain {
+    const float *params, *target;
+    const float *r_state, *r_state_prime, *r_reward;
+    const int8_t* r_action;
+    const uint8_t* r_done;
+    const unsigned long long* r_count;
+    long long r_capacity;
+    float* priority;
+    unsigned long long* seen;
+    float gamma, prio_e, prio_a;
+};
+struct StampArgs {
+    StampBrain b[RL_MAX_CAPTURE_BRAINS];
+};
+
+constexpr int kSLdsFloats = kTRows * kTXS + 2 * kTRows * kTHS + kTRows * 8 + 3 * kTRows;
+constexpr int kSLdsBytes = kSLdsFloats * 4;
+static_assert(2 * (kSLdsBytes + 1024) <= 160 * 1024, "two k_td_stamp workgroups must fit a CU's 160 KiB");
+
+__global__ __launch_bounds__(kTBlock) void k_td_stamp(const StampArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float td_lds[];
+    float* xs = td_lds;                             // X  [64][156]
+    float* h1 = xs + kTRows * kTXS;                 // H1 [64][68]
+    float* h2 = h1 + kTRows * kTHS;                 // H2 [64][68]
+    float* q = h2 + kTRows * kTHS;                  // [64][8]
+    float* row_r = q + kTRows * 8;                  // [64] reward
+    float* row_mask = row_r + kTRows;               // [64] 1 - done
+    float* row_y = row_mask + kTRows;               // [64] max q'
+    __shared__ int row_slot[kTRows];
+    __shared__ int row_a[kTRows];
+
+    const int tid = threadIdx.x;
+    const StampBrain& B = A.b[blockIdx.y];
+    const unsigned long long count = *B.r_count, seen = *B.seen, cap = (unsigned long long)B.r_capacity;
+    const unsigned long long size = count < cap ? count : cap;
+    const unsigned long long fresh = count > seen ? count - seen : 0ull;   // rows appended since the last draw (k_prio_prepare's rule)
+    const bool all = fresh >= cap;
+    const unsigned long long n_window = all ? size : fresh;
+    const unsigned long long j0 = (unsigned long long)blockIdx.x * kTRows;
+    if (j0 >= n_window) return;                     // (uniform) beyond the window
+
+    if (tid < kTRows) {   // window row j sits in slot j (the whole ring) or (seen + j) mod capacity: always < size <= capacity
+        const unsigned long long j = j0 + tid;
+        const bool in = j < n_window;
+        const int slot = in ? (int)(all ? j : (seen % cap + j) % cap) : 0;
+        row_slot[tid] = in ? slot : -1;
+        row_a[tid] = in ? (int)B.r_action[slot] & 7 : 0;
+        row_r[tid] = in ? B.r_reward[slot] : 0.0f;
+        row_mask[tid] = in ? (B.r_done[slot] ? 0.0f : 1.0f) : 0.0f;
+    }
+    __syncthreads();
+    td_stage_rows(B.r_state_prime, row_slot, xs, tid);
+    __syncthreads();
+    // ---- max_a Q_target(s') ----
+    td_network(B.target, xs, h1, h2, q, tid);
+    if (tid < kTRows) {
+        float mx = q[tid * 8];
+        for (int a = 1; a < 8; ++a) mx = fmaxf(mx, q[tid * 8 + a]);
+        row_y[tid] = mx;
+    }
+    td_stage_rows(B.r_state, row_slot, xs, tid);    // (the target forward is done with X)
+    __syncthreads();
+    // ---- Q(s) and the rows' priorities: k_learn_perdqn's expressions ----
+    td_network(B.params, xs, h1, h2, q, tid);
+    if (tid < kTRows && row_slot[tid] >= 0) {
+        const float target = row_r[tid] + row_mask[tid] * (B.gamma * row_y[tid]);
+        const float td = q[tid * 8 + row_a[tid]] - target;
+        B.priority[row_slot[tid]] = powf(fabsf(td) + B.prio_e, B.prio_a);
+    }
+}
+
+// the launch behind k_td_stamp, its only reader of `seen`: one thread per learner
+__global__ __launch_bounds__(64) void k_td_stamp_seen(const StampArgs A, int n_learners)
+{
+    const int i = threadIdx.x;
+    if (i < n_learners) *A.b[i].seen = *A.b[i].r_count;
+}
+
 }  // namespace
+
+int rl_learn_td_stamp_launch(rl_world*, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, hipStream_t stream)
+{
+    StampArgs a{};
+    long long max_cap = 1;
+    for (int i = 0; i < n_learners; ++i) {
+        const rl_learner& l = learners[i];
+        const rl_replay& r = rings[i];
+        StampBrain& b = a.b[i];
+        b.params = l.params; b.target = l.target;
+        b.r_state = r.state; b.r_state_prime = r.state_prime; b.r_reward = r.reward; b.r_action = r.action; b.r_done = r.done;
+        b.r_count = r.count; b.r_capacity = r.capacity;
+        b.priority = tds[i].priority; b.seen = tds[i].seen;
+        b.gamma = l.gamma; b.prio_e = tds[i].prio_e; b.prio_a = tds[i].prio_a;
+        max_cap = r.capacity > max_cap ? r.capacity : max_cap;
+    }
+    {   // 76 KB of dynamic LDS: asked for at every call, as rl_learn_td does
+        const hipError_t e = hipFuncSetAttribute((const void*)k_td_stamp, hipFuncAttributeMaxDynamicSharedMemorySize, kSLdsBytes);
+        if (e != hipSuccess) { rl_set_error("rl_learn_td_stamp: hipFuncSetAttribute(%d bytes of LDS) failed: %s", kSLdsBytes, hipGetErrorString(e)); return RL_E_LAUNCH; }
+    }
+    hipLaunchKernelGGL(k_td_stamp, dim3((unsigned)((max_cap + kTRows - 1) / kTRows), n_learners), dim3(kTBlock), kSLdsBytes, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { rl_set_error("rl_learn_td_stamp: launch of the stamp kernel failed: %s", hipGetErrorString(e)); return RL_E_LAUNCH; }
+    hipLaunchKernelGGL(k_td_stamp_seen, dim3(1), dim3(64), 0, stream, a, n_learners);
+    e = hipGetLastError();
+    if (e != hipSuccess) { rl_set_error("rl_learn_td_stamp: launch of the window kernel failed: %s", hipGetErrorString(e)); return RL_E_LAUNCH; }
+    return RL_OK;
+}
 
 int rl_learn_td_supported_impl(int kind) { return kind == RL_PERDQN ? 1 : 0; }
 

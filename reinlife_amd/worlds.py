@@ -522,6 +522,23 @@ class DeviceWorlds:
         return self._draw_side_rank("draw_td_rank", "rl_learn_td_draw_rank", learners, n_steps, stratified, _lib.TdPrio,
                                     "a PERDQN one (DeviceLearner(..., td_priority=True))")
 
+    def stamp_td(self, learners):
+        """This build's own, in front of draw_td() / draw_td_rank() (rl_learn_td_stamp, two launches): every row appended since the last
+        draw gets the priority append_sample spells out and does not compute, (|Q(s)[a] - (r + (1 - done) gamma max_a Q_target(s'))| +
+        e) ** a, from a forward pass of learner.target and learner.params as they stand now -- bit for bit what learn() would write for
+        the row from the same parameters -- and learner.seen moves up to the ring's count, so the draw that follows stamps nothing.
+        The learners may differ in batch (it is not read).  Returns nothing; queued on the current stream."""
+        n = len(learners)
+        if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
+            raise ValueError("stamp_td(): 1 to %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
+        if any(l.spec.side is not _lib.TdPrio for l in learners):
+            raise ValueError("stamp_td(): every learner must be a PERDQN one (DeviceLearner(..., td_priority=True))")
+        arr = (_lib.Learner * n)(*[l.struct() for l in learners])
+        rings = (_lib.Replay * n)(*[l.ring_struct() for l in learners])
+        sides = (_lib.TdPrio * n)(*[l.side_struct(_lib.TdPrio) for l in learners])
+        _lib.check(self.lib.rl_learn_td_stamp(self.handle, arr, rings, sides, n, self._stream()), "rl_learn_td_stamp")
+        self.launches += _lib.LEARN_TD_STAMP_LAUNCHES
+
     def _draw_side_rank(self, who, draw, learners, n_steps, stratified, side, one_of):
         """draw_prioritized_rank / draw_td_rank: the C entry `draw`, fed the learners' side structs and their order / cum / work buffers.
         The learners of a call must share one batch -- deliberately, as for every draw_* here: the table comes back as ONE tensor
