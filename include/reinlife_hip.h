@@ -25,6 +25,8 @@
  *   rl_learn_td_stamp  this build's own: the rows appended since the last draw get the TD-error priority PERDQN.py:113-128 spells out
  *                      and does not compute (a forward pass of both networks per fresh row)
  *   rl_learn_ppo       PPO.learn(): k_epoch full-batch Adam steps on a rollout of at most 32 rows (rl_learn_rollout draws it)
+ *   rl_learn_ppo_wide  PPO.learn() on a rollout of up to 2048 rows, 32-row tiles side by side, ONE GAE recursion over the whole rollout
+ *                      (rl_learn_rollout_wide draws it)
  *   rl_learn_dueling   D3QNAgent.train(): one minibatch update of the dueling network (MSE, Adam), batch up to 64
  *                      Models/D3QN.py:97-116, 148-165 (schedule and target copy of :118-126: the caller's)
  *
@@ -740,6 +742,65 @@ int rl_learn_ppo(rl_world* h, const rl_learner* learners, const rl_replay* rings
  * unused; a launch that appends more than a ring holds keeps rows by append order. */
 int rl_learn_rollout(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_ppo* ppos, int n_learners, int n_steps,
                      int32_t* slots, void* stream);
+
+/* ---- on-policy learning on wide rollouts (PPO) ------------------------------------------------------------------- */
+/* The TILING is this build's own; the length is not: PPO.learn() (PPO.py:136-162) trains on the WHOLE list gathered since the last call,
+ * which rl_learn_ppo cannot express once it passes 32 rows.  rl_learn_ppo_wide is rl_learn_ppo on a rollout of 1 ..
+ * RL_LEARN_PPO_WIDE_MAX rows, computed in 32-row tiles with one workgroup per (learner, tile), with ONE GAE recursion over the whole
+ * rollout.  A call whose batch is at most 32 (one tile), given the same slots, leaves every buffer rl_learn_ppo writes -- params,
+ * adam_m, adam_v, state, packed, loss, grad -- with rl_learn_ppo's bits.  rl_learn_ppo, rl_learn_rollout and every *_supported answer
+ * are unchanged by it. */
+#define RL_LEARN_PPO_WIDE_MAX 2048
+/* 1 for the brain kinds rl_learn_ppo_wide trains (RL_PPO), 0 for the others */
+int rl_learn_ppo_wide_supported(int kind);
+/* The bytes of one learner's work buffer for a rollout of `batch` rows, T = ceil(batch / 32) tiles:
+ *   64 + T * (16 + 256 + 4 * 107,529) = 64 + 430,388 T          (27,544,896 bytes at 2048 rows)
+ *   a 64-byte header | lsum[T][2] float64: the tiles' sums of the two loss terms | td[32 T] | delta[32 T] float32: what the two tile
+ *   passes exchange | partial[T][107,529] float32: the tiles' gradients.
+ * 0, with rl_last_error set, for a kind rl_learn_ppo_wide does not train or a batch outside [1, RL_LEARN_PPO_WIDE_MAX]. */
+size_t rl_learn_ppo_wide_work_bytes(int kind, int batch);
+/* rl_learn_rollout for wide rollouts: the same two launches (prepare, pick) with the same arithmetic, batch in
+ * [1, RL_LEARN_PPO_WIDE_MAX] and ONE batch for all learners of a call.  Draw d = s * batch + j keeps its salt -- words 0-1 of
+ * rl_philox(seed, 0, i, (uint32)state[1], RL_SITE_LEARN_ROLLOUT, d) -- so with batch <= 32 the table, keys, *fresh and *seen are
+ * rl_learn_rollout's, bit for bit.  n_steps x batch workgroups per learner, each a pass over the window's rows.
+ *   slots     device int32 [n_learners][n_steps][batch]
+ * Everything else -- the window, kind RL_PPO (anything else: RL_E_UNSUPPORTED naming the kind), the rings' columns (age included), seen /
+ * fresh / keys of every rl_ppo, n_steps in [1,65536], the deviations (with replacement, by content key) -- is as rl_learn_rollout states it. */
+int rl_learn_rollout_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_ppo* ppos, int n_learners, int n_steps,
+                          int32_t* slots, void* stream);
+/* PPO.learn() (PPO.py:136-162) on wide rollouts for n_learners brains, on the rl_learner / rl_replay / rl_ppo structures of rl_learn_ppo.
+ *   batch       learners[i].batch in [1, RL_LEARN_PPO_WIDE_MAX], ONE batch for all learners of a call; slots is device int32
+ *               [n_learners][n_steps][batch].  Tile t of a rollout holds its rows 32 t .. min(32 t + 31, batch - 1).
+ *   work        host array [n_learners] of caller-owned device scratch of rl_learn_ppo_wide_work_bytes bytes each, 16-byte aligned.  It
+ *               needs no initialisation and carries nothing between calls.
+ *   a rollout   per epoch rl_learn_ppo's arithmetic on every row -- the forward passes, the per-row scalars formed in double and rounded
+ *               once, the tie and clamp rules of the gradients, reward / 100 in double -- with three rules in place of its one-workgroup ones:
+ *               1. ONE GAE chain over the whole rollout: adv_t = fl(fl(gl adv_(t+1)) + delta_t), gl = (float)(gamma * lmbda), backwards from
+ *                  row batch - 1 to row 0 in float32, one multiply and one add, no fma, no reset at done, whatever tile a row sits in.  A
+ *                  row's delta = td - v(s) does not depend on its place in a tile (its forward arithmetic is k ascending everywhere).
+ *               2. means over the whole rollout: both loss terms and their gradients are scaled by 1 / (float)batch of the WHOLE batch.
+ *                  Rows of the last tile beyond the batch are zero rows with zero loss gradients and stay out of the chain.
+ *               3. a tile stores its partial gradient, each parameter summed in rl_learn_ppo's order over the tile's rows; one thread per
+ *                  parameter adds the tiles' partials in tile order in double, rounds to float once and makes rl_learn_ppo's Adam update
+ *                  with the bias corrections of step state[0] as read at entry + the epochs made so far in the call + 1.
+ *               loss[s][ep] = (float)(L1 / (double)batch + L2 / (double)batch), L1 and L2 the per-tile double sums of the rows' two loss
+ *               terms (rows ascending) added in tile order from 0.0; grad[s * k_epoch + ep][n_params] is the summed, rounded gradient.
+ *   fresh       ppos[i].fresh given and *fresh == 0: no update and no slot check; only state[1] moves.
+ *   bad slots   every slot of a call that trains is range-checked against [0, min(count, capacity)) in a pass of its own before a row is
+ *               fetched: a bad one sets error-flag code 6 ([1] = learner, [2] = step, [3] = the value; the first in table order) and
+ *               NONE of that learner's buffers is written; the other learners train.
+ *   afterwards  state[0] += k_epoch per rollout trained; state[1] += 1; `packed` is rewritten from the final params (rl_policy_pack_device's
+ *               kernel: bit for bit what rl_policy_pack_weights(RL_PPO, ...) makes).
+ * 3 n_steps K + 3 launches, K = the largest k_epoch among the call's learners, all queued on `stream`: the check; per rollout and epoch
+ * the two tile passes (grid T x n_learners) and the update; the counters; the packer.  A learner with a smaller k_epoch sits out the
+ * later epochs.  No host read-back, no cooperative launch, no workgroup waits for another, no allocation, no float atomics: the same
+ * buffers give the same bits in every run and whatever else is in the launch.
+ * Validated on the host before anything is launched: kind must be RL_PPO (anything else: RL_E_UNSUPPORTED naming the kind); otherwise
+ * RL_E_INVALID naming the argument: null handle / learners / rings / ppos / work, a null work[i], slots == NULL (the draw is
+ * rl_learn_rollout_wide's job), n_learners in [1, RL_MAX_CAPTURE_BRAINS], n_steps in [1,65536], batch in [1, RL_LEARN_PPO_WIDE_MAX] and
+ * equal for all learners, k_epoch in [1,8], lmbda and eps_clip >= 0, rl_learn_ppo's null-pointer and capacity checks, a ring without `prob`. */
+int rl_learn_ppo_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_ppo* ppos, int n_learners, int n_steps,
+                      const int32_t* slots, void* const* work, void* stream);
 
 /* ---- prioritised replay with importance weights (PERDQN) ---------------------------------------------------------- */
 /* The prioritised memory of one learning PERDQN brain (Memory / SumTree, Models/PERDQN.py) beside its rl_replay ring: caller-owned

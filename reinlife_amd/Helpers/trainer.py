@@ -134,6 +134,13 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     gate (exploration, one row), ONE update per call, target sync rule, learning rate and learn_ranks are the PERD3QN learners'; a call
     is 2 + 6 launches instead of 2 + 1.  {"PERD3QN": 64} gives the learners that learn_prioritized=True alone gives, bit for bit,
     priorities and prio_max included.
+    With learn_rollout=True (and only then: without it the key stays unknown) the dict also takes "PPO": every PPO learner trains through
+    rl_learn_ppo_wide on rollouts of B rows in [1, 2048] -- PPO.learn() (PPO.py:136-162) trains on the whole list gathered since the last
+    call, which rl_learn_ppo's 32 rows cannot express; the tiling is this build's own: 32-row tiles side by side, ONE GAE recursion over
+    the whole rollout across the tiles, both means over all B rows, the tiles' gradients summed in tile order in double -- the same bits
+    in every run.  The draw is rl_learn_rollout_wide (the on-policy draw at that width: with replacement, by content key);
+    rollout_steps, schedule, the empty-window gate, k_epoch, learning rate and learn_ranks are the PPO learners'; a call is
+    2 + 3 rollout_steps k_epoch + 3 launches instead of 2 + 1.  {"PPO": 32} gives the learners that learn_rollout=True alone gives, bit for bit.
     learn_draw (default None: every run is launch for launch and bit for bit what it was; "rank" needs learn="device" and at least one
     brain of the learning kinds -- one that rl_learn, rl_learn_wide or rl_learn_dueling trains -- anything else is a ValueError before a
     device is touched): THIS BUILD'S OWN.  The DQN, wide DQN and D3QN learners' minibatches are then drawn by rl_learn_draw_rank instead of

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..learn import BUFFER_LIMIT, ENTRIES, ENTRY, ENTRY_BY_METHOD, FAMILIES, DeviceLearner, entry_of
+from ..learn import ALL_ENTRIES as ENTRIES, BUFFER_LIMIT, ENTRY, ENTRY_BY_METHOD, FAMILIES, DeviceLearner, entry_of
 from ..worlds import DeviceWorlds
 from .utils import Actions, EntityTypes
 
@@ -207,6 +207,8 @@ class Environment:
         # on minibatches of B rows in 64-row tiles, the advantage mean taken over the whole batch (the reference's minibatch is 64, D3QN.py:98).
         # With learn_prioritized=True the dict also takes "PERD3QN": every PERD3QN learner trains through rl_learn_prioritized_wide on
         # minibatches of B rows (the prioritised draw at that width, the priorities of all B rows written); without it the key stays unknown.
+        # With learn_rollout=True the dict also takes "PPO": every PPO learner trains through rl_learn_ppo_wide on rollouts of B rows (1 ..
+        # 2048) in 32-row tiles, ONE GAE recursion over the whole rollout (the on-policy draw at that width); without it the key stays unknown.
         wide = {e.method: e for e in ENTRIES if e.narrow}   # the wide entry per brain method, a key of the dict only where its narrow entry is on
         self.learn_batch_of = dict.fromkeys(wide)
         if isinstance(learn_batch, dict):
@@ -214,7 +216,8 @@ class Environment:
             unknown = [k for k in learn_batch if k not in on]
             if unknown or not learn_batch:
                 raise ValueError("learn_batch as a dict takes the keys 'DQN' (rl_learn_wide) and 'D3QN' (rl_learn_dueling_wide)%s and at least one of them, got %r"
-                                 % (" and, with learn_prioritized=True, 'PERD3QN' (rl_learn_prioritized_wide)," if self.learn_prioritized else "", learn_batch))
+                                 % ((" and, with learn_prioritized=True, 'PERD3QN' (rl_learn_prioritized_wide)," if self.learn_prioritized else "")
+                                    + (" and, with learn_rollout=True, 'PPO' (rl_learn_ppo_wide)," if self.learn_rollout else ""), learn_batch))
             for k, v in learn_batch.items():
                 limit = getattr(_lib, on[k].batch_max)
                 if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= limit:
@@ -774,12 +777,15 @@ class Environment:
         "rl_learn_ppo": (True, "%(steps)d rollout(s) of %(batch)s rows, %(k_epoch)s Adam steps each, every %(every)d episodes; the rows are "
                          "drawn by content key with replacement from those appended since the last call, so the GAE's neighbours are unrelated rows "
                          "and the other fresh rows go unused"),
+        "rl_learn_ppo_wide": (True, "%(steps)d rollout(s) of %(wide)d rows (learn_batch) in 32-row tiles, one GAE recursion over the whole "
+                              "rollout, %(k_epoch)s Adam steps each, every %(every)d episodes; the rows are drawn by content key with replacement "
+                              "from those appended since the last call, so the GAE's neighbours are unrelated rows and the other fresh rows go unused"),
         "rl_learn_td": (True, "%(steps)d minibatch update(s) of batch %(batch)s every %(every)d episodes once the ring holds the "
                         "brain's train_start rows, loss scaled by the mean importance weight, target synced at every call, rows drawn with "
                         "probability priority / sum by content key with replacement -- independent draws, not the reference's stratified ones; "
                         "every new row gets the reference's one priority (0 + 0.01) ** 0.6; epsilon decays once per update"),
     }
-    assert set(_NOTES) == set(ENTRY), "every row of learn.ENTRIES needs its note"
+    assert set(_NOTES) == set(ENTRY), "every row of learn.ALL_ENTRIES needs its note"
 
     def _steps(self, family):
         """The updates (PPO: rollouts) one learning call makes for the learners of `family`."""
@@ -872,6 +878,10 @@ class Environment:
         place, the same way -- gate, target rule, ONE step, draw (rl_learn_prioritized_wide_draw, two launches) then learn (6 launches
         instead of one) --, behind the DQN and D3QN calls; B = 64 draws rl_learn_prioritized's rows and ends with its bits, priorities and
         prio_max included.
+        learn_batch={"PPO": B} (with learn_rollout=True): the PPO learners are wide ones (rl_learn_ppo_wide, rollouts of B rows in 32-row
+        tiles, one GAE recursion over the whole rollout) and are called in the PPO learners' place, the same way -- no gate but the empty
+        window, `rollout_steps` rollouts, draw (rl_learn_rollout_wide, two launches) then learn (3 rollout_steps k_epoch + 3 launches
+        instead of one) --; B = 32 draws rl_learn_rollout's rows and ends with rl_learn_ppo's bits.
         learn_draw="rank": the draw_slots calls above -- the DQN, wide DQN and D3QN learners' -- are draw_slots_rank calls (rl_learn_draw_rank,
         six launches instead of two: the rings' rows sorted by content key once, every draw an index into that order); the prioritised,
         rollout and PERDQN draws are what they are.

@@ -96,6 +96,7 @@ LEARN_DRAW_RANK_LAUNCHES = 6   # RL_LEARN_DRAW_RANK_LAUNCHES: the launches of on
 LEARN_PRIO_DRAW_RANK_LAUNCHES = 8   # RL_LEARN_PRIO_DRAW_RANK_LAUNCHES: the launches of one rl_learn_prioritized_draw_rank / rl_learn_td_draw_rank call
 LEARN_TD_STAMP_LAUNCHES = 2   # RL_LEARN_TD_STAMP_LAUNCHES: the launches of one rl_learn_td_stamp call
 PPO_ROLLOUT_MAX = 32   # RL_PPO_ROLLOUT_MAX: the rows of a rollout at most (rl_learn_ppo)
+LEARN_PPO_WIDE_MAX = 2048   # RL_LEARN_PPO_WIDE_MAX: the rows of a rollout at most (rl_learn_ppo_wide)
 
 
 class Brain(C.Structure):
@@ -158,6 +159,10 @@ ABI = [
     ("rl_learn_ppo_supported", C.c_int, [C.c_int]),
     ("rl_learn_ppo", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Ppo), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_rollout", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Ppo), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_ppo_wide_supported", C.c_int, [C.c_int]),
+    ("rl_learn_ppo_wide_work_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("rl_learn_rollout_wide", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Ppo), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_ppo_wide", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Ppo), C.c_int, C.c_int, _P, C.POINTER(_P), _P]),
     ("rl_learn_td_supported", C.c_int, [C.c_int]),
     ("rl_learn_td_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_td_draw_rank", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),

@@ -7,7 +7,7 @@
 
 #include "rl_common.h"
 
-// implemented in rl_world.hip / rl_policy.hip / rl_render.hip / rl_learn.hip / rl_learn_dueling.hip / rl_learn_prio.hip / rl_learn_td.hip / rl_learn_merge.hip / rl_learn_wide.hip / rl_learn_dueling_wide.hip (also rl_learn_prioritized_wide)
+// implemented in rl_world.hip / rl_policy.hip / rl_render.hip / rl_learn.hip / rl_learn_dueling.hip / rl_learn_prio.hip / rl_learn_td.hip / rl_learn_merge.hip / rl_learn_wide.hip / rl_learn_dueling_wide.hip (also rl_learn_prioritized_wide) / rl_learn_ppo_wide.hip
 size_t rl_world_smem_bytes(int cpad, int cap, int hash, int plane_stride, int height);
 int rl_world_block();
 int rl_world_launch_step(rl_world*, const int8_t*, const rl_tape*, const rl_step_out*, hipStream_t);
@@ -56,6 +56,10 @@ int rl_learn_td_stamp_launch(rl_world*, const rl_learner*, const rl_replay*, con
 int rl_learn_ppo_supported_impl(int);
 int rl_learn_ppo_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, const int32_t*, hipStream_t);
 int rl_learn_rollout_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, int32_t*, hipStream_t);
+int rl_learn_ppo_wide_supported_impl(int);
+size_t rl_learn_ppo_wide_work_bytes_impl(int);
+int rl_learn_ppo_wide_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, const int32_t*, void* const*, hipStream_t);
+int rl_learn_rollout_wide_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, int32_t*, hipStream_t);
 int64_t rl_learn_merge_floats_impl(int);
 int rl_learn_export_launch(rl_world*, const rl_learner*, int, float*, hipStream_t);
 int rl_learn_merge_launch(rl_world*, const rl_learner*, int, const float*, int, int64_t, hipStream_t);
@@ -699,29 +703,34 @@ int rl_learn_prioritized_wide(rl_world* h, const rl_learner* learners, const rl_
 int rl_learn_ppo_supported(int kind) { return rl_learn_ppo_supported_impl(kind); }
 
 // what rl_learn_ppo and rl_learn_rollout ask of their common arguments (`draw`: the rollout draw needs the rings' age column and
-// seen / fresh / keys of rl_ppo; the update needs the learner's buffers and the rings' prob column)
+// seen / fresh / keys of rl_ppo; the update needs the learner's buffers and the rings' prob column).  The wide pair (rl_learn_ppo_wide,
+// rl_learn_rollout_wide) asks the same with its own batch limit, and ONE batch for all learners of a call: `max_batch`, `one_batch`, the
+// name of the *_supported answer and of the draw.
 static int check_ppo(const char* who, bool draw, rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_ppo* ppos,
-                     int n_learners, int n_steps, const void* slots)
+                     int n_learners, int n_steps, const void* slots, int max_batch = RL_PPO_ROLLOUT_MAX, bool one_batch = false,
+                     const char* supported = "rl_learn_ppo_supported", const char* drawn_by = "rl_learn_rollout")
 {
     if (!h) { rl_set_error("%s: null handle", who); return RL_E_INVALID; }
     if (!learners || !rings || !ppos) { rl_set_error("%s: null learners / rings / ppos", who); return RL_E_INVALID; }
     if (n_learners < 1 || n_learners > RL_MAX_CAPTURE_BRAINS) { rl_set_error("%s: n_learners must be in [1,%d] (got %d)", who, RL_MAX_CAPTURE_BRAINS, n_learners); return RL_E_INVALID; }
     if (n_steps < 1 || n_steps > 65536) { rl_set_error("%s: n_steps must be in [1,65536] (got %d)", who, n_steps); return RL_E_INVALID; }
     if (!slots) {
-        rl_set_error(draw ? "%s: slots must not be null" : "%s: slots must not be null -- the rows of a rollout are drawn by rl_learn_rollout (or named by the caller)", who);
+        if (draw) rl_set_error("%s: slots must not be null", who);
+        else rl_set_error("%s: slots must not be null -- the rows of a rollout are drawn by %s (or named by the caller)", who, drawn_by);
         return RL_E_INVALID;
     }
     for (int i = 0; i < n_learners; ++i) {
         const rl_learner& l = learners[i];
         const rl_replay& r = rings[i];
         const rl_ppo& p = ppos[i];
-        if (!rl_learn_ppo_supported_impl(l.kind)) { rl_set_error("%s: learner %d has brain kind %d; this entry point trains RL_PPO (3) only (rl_learn_ppo_supported)", who, i, l.kind); return RL_E_UNSUPPORTED; }
+        if (!rl_learn_ppo_supported_impl(l.kind)) { rl_set_error("%s: learner %d has brain kind %d; this entry point trains RL_PPO (3) only (%s)", who, i, l.kind, supported); return RL_E_UNSUPPORTED; }
         if (draw) {
             if (!l.state) { rl_set_error("%s: learner %d: state must not be null", who, i); return RL_E_INVALID; }
         } else if (!l.params || !l.adam_m || !l.adam_v || !l.state || !l.packed) {
             rl_set_error("%s: learner %d: params / adam_m / adam_v / state / packed must not be null", who, i); return RL_E_INVALID;
         }
-        if (l.batch < 1 || l.batch > RL_PPO_ROLLOUT_MAX) { rl_set_error("%s: learner %d: batch (the rows of a rollout) must be in [1,%d] (got %d)", who, i, RL_PPO_ROLLOUT_MAX, l.batch); return RL_E_INVALID; }
+        if (l.batch < 1 || l.batch > max_batch) { rl_set_error("%s: learner %d: batch (the rows of a rollout) must be in [1,%d] (got %d)", who, i, max_batch, l.batch); return RL_E_INVALID; }
+        if (one_batch && l.batch != learners[0].batch) { rl_set_error("%s: learner %d: batch %d differs from learner 0's %d (the learners of a call share one batch)", who, i, l.batch, learners[0].batch); return RL_E_INVALID; }
         if (!r.state || !r.state_prime || !r.action || !r.reward || !r.done || !r.count || (draw && !r.age) || r.capacity < 1 || r.capacity > 0x7fffffff) {
             rl_set_error("%s: replay %d incomplete (state / state_prime / action / reward / done / %scount, capacity in [1, 2^31))", who, i, draw ? "age / " : ""); return RL_E_INVALID;
         }
@@ -750,6 +759,36 @@ int rl_learn_rollout(rl_world* h, const rl_learner* learners, const rl_replay* r
     if (int rc = check_ppo("rl_learn_rollout", true, h, learners, rings, ppos, n_learners, n_steps, slots)) return rc;
     DeviceGuard guard(device_of_pointer(slots));
     return rl_learn_rollout_launch(h, learners, rings, ppos, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+int rl_learn_ppo_wide_supported(int kind) { return rl_learn_ppo_wide_supported_impl(kind); }
+
+size_t rl_learn_ppo_wide_work_bytes(int kind, int batch)
+{
+    if (!rl_learn_ppo_wide_supported_impl(kind)) { rl_set_error("rl_learn_ppo_wide_work_bytes: brain kind %d; rl_learn_ppo_wide trains RL_PPO (3) only (rl_learn_ppo_wide_supported)", kind); return 0; }
+    if (batch < 1 || batch > RL_LEARN_PPO_WIDE_MAX) { rl_set_error("rl_learn_ppo_wide_work_bytes: batch must be in [1,%d] (got %d)", RL_LEARN_PPO_WIDE_MAX, batch); return 0; }
+    return rl_learn_ppo_wide_work_bytes_impl(batch);
+}
+
+int rl_learn_rollout_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_ppo* ppos, int n_learners, int n_steps,
+                          int32_t* slots, void* stream)
+{
+    if (int rc = check_ppo("rl_learn_rollout_wide", true, h, learners, rings, ppos, n_learners, n_steps, slots, RL_LEARN_PPO_WIDE_MAX, true,
+                           "rl_learn_ppo_wide_supported", "rl_learn_rollout_wide")) return rc;
+    DeviceGuard guard(device_of_pointer(slots));
+    return rl_learn_rollout_wide_launch(h, learners, rings, ppos, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+int rl_learn_ppo_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_ppo* ppos, int n_learners, int n_steps,
+                      const int32_t* slots, void* const* work, void* stream)
+{
+    if (h && !work) { rl_set_error("rl_learn_ppo_wide: null work"); return RL_E_INVALID; }
+    if (int rc = check_ppo("rl_learn_ppo_wide", false, h, learners, rings, ppos, n_learners, n_steps, slots, RL_LEARN_PPO_WIDE_MAX, true,
+                           "rl_learn_ppo_wide_supported", "rl_learn_rollout_wide")) return rc;
+    for (int i = 0; i < n_learners; ++i)
+        if (!work[i]) { rl_set_error("rl_learn_ppo_wide: work[%d] must not be null (rl_learn_ppo_wide_work_bytes)", i); return RL_E_INVALID; }
+    DeviceGuard guard(device_of_pointer(learners[0].params));
+    return rl_learn_ppo_wide_launch(h, learners, rings, ppos, n_learners, n_steps, slots, work, (hipStream_t)stream);
 }
 
 int rl_render(rl_world* h, const rl_render_style* style, const int32_t* worlds, int n_frames, uint8_t* frames, void* stream)

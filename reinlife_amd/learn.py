@@ -1,4 +1,4 @@
-"""DeviceLearner: what a DQN (also on wide minibatches: wide_batch=, rl_learn_wide), D3QN (also on wide minibatches: dueling_batch=, rl_learn_dueling_wide), (prioritized=True) PERD3QN, (rollout=True) PPO or (td_priority=True) PERDQN brain needs to learn on
+"""DeviceLearner: what a DQN (also on wide minibatches: wide_batch=, rl_learn_wide), D3QN (also on wide minibatches: dueling_batch=, rl_learn_dueling_wide), (prioritized=True) PERD3QN, (rollout=True) PPO (also on wide rollouts: rollout_batch=, rl_learn_ppo_wide) or (td_priority=True) PERDQN brain needs to learn on
 the device (rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo / rl_learn_td, include/reinlife_hip.h) -- the flat f32 master parameters,
 the target network, Adam's moments, the step / call counters and the packed weights the acting kernels read, all as device tensors.
 
@@ -32,7 +32,10 @@ carry the acting probability (enable_capture(..., with_prob=True)) -- the bookke
 rollout, the rows the last window held, and the draw's scratch keys (DeviceWorlds.draw_rollout: `batch` = 32 rows per rollout, drawn
 uniformly with replacement by content key from the rows appended since the last call).  Deviations: the schedule is the caller's; a rollout
 is 32 independent draws, so the GAE recursion's neighbours are unrelated rows (in the reference: unrelated agents of one tick); the fresh
-rows not drawn go unused.
+rows not drawn go unused.  DeviceLearner(brain, device, ring, rollout=True, rollout_batch=B) is the same learner on wide rollouts of
+B <= 2048 rows (rl_learn_ppo_wide: 32-row tiles side by side with ONE GAE recursion over the whole rollout, both means over all B rows;
+the tiling is this build's own, the length is not -- PPO.learn() trains on the whole list, however long); it also owns that entry
+point's work buffer, and its draw is rl_learn_rollout_wide.
 
 PERDQNAgent (ReinLife/Models/PERDQN.py) owns `model`, `target_model`, `memory` (a sum tree of priorities) and `optimizer`; train_model()
 makes one Adam step on a minibatch of 64 drawn by priority.  DeviceLearner(brain, device, ring, td_priority=True) is that agent's learner
@@ -83,6 +86,7 @@ class Entry(NamedTuple):
     side_tensors: tuple = ()         # ... and the learner tensors that struct is made of (SIDE_TENSORS)
     draw: str = None                 # its own draw entry (None: the uniform draws, draw_slots / draw_slots_rank)
     launches: Callable = lambda n_steps: 1   # what one call of n_steps counts as
+    per_epoch: bool = False          # launches takes (n_steps, k_epoch): the count depends on the largest k_epoch among the call's learners
 
     supported = property(lambda e: e.name + "_supported")
     work_bytes = property(lambda e: e.name + "_work_bytes" if e.narrow else None)
@@ -109,9 +113,19 @@ ENTRIES = (
           batch_max="LEARN_PRIORITIZED_WIDE_MAX", one_batch=True, draw="rl_learn_prioritized_wide_draw",
           launches=lambda n_steps: 3 * n_steps + 3, **_PRIO),   # as rl_learn_dueling_wide
 )
-ENTRY = {e.name: e for e in ENTRIES}
-ENTRY_BY_METHOD = {e.method: e.name for e in ENTRIES if not e.keyword}   # the brain kinds an entry point trains without a keyword (Environment's learn_kinds)
-assert all(e.family in FAMILIES and set(e.side_tensors) <= set(SIDE_TENSORS) for e in ENTRIES) and set(ENTRY_BY_METHOD.values()) <= set(ENTRY)
+# ENTRIES stays these eight rows: tests count them (tests/test_learn_td_stamp_cpu.py, tests/test_learn_prio_draw_rank_cpu.py).  The rows added
+# since stand in MORE_ENTRIES, and the layer reads ALL_ENTRIES = ENTRIES + MORE_ENTRIES: what is said above of a row's index and of the order
+# the keyword rows are tried in holds for that table, and a new row goes to the END of MORE_ENTRIES.
+MORE_ENTRIES = (
+    Entry("rl_learn_ppo_wide", "PPO", "ppo", has_target=False, keyword="rollout_batch", needs="rollout",
+          conflicts=("wide_batch", "dueling_batch", "prioritized", "prioritized_batch", "td_priority"), narrow="rl_learn_ppo",
+          batch_max="LEARN_PPO_WIDE_MAX", one_batch=True, side=_lib.Ppo, side_tensors=("keys", "seen", "fresh"), draw="rl_learn_rollout_wide",
+          launches=lambda n_steps, k_epoch: 3 * n_steps * k_epoch + 3, per_epoch=True),   # check, the two tile passes and the update per rollout and epoch, counters, pack
+)
+ALL_ENTRIES = ENTRIES + MORE_ENTRIES
+ENTRY = {e.name: e for e in ALL_ENTRIES}
+ENTRY_BY_METHOD = {e.method: e.name for e in ALL_ENTRIES if not e.keyword}   # the brain kinds an entry point trains without a keyword (Environment's learn_kinds)
+assert all(e.family in FAMILIES and set(e.side_tensors) <= set(SIDE_TENSORS) for e in ALL_ENTRIES) and set(ENTRY_BY_METHOD.values()) <= set(ENTRY)
 
 
 def entry_of(kind):
@@ -125,13 +139,16 @@ def _spelled(keyword):
 
 
 class DeviceLearner:
-    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False, td_priority=False, prioritized_batch=None, wide_batch=None, dueling_batch=None):
+    def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False, td_priority=False, prioritized_batch=None, *,
+                 rollout_batch=None, wide_batch=None, dueling_batch=None):
+        # (the keywords behind `*` are keyword-only: rollout_batch stands in front of wide_batch and dueling_batch, whose place as the
+        # signature's last two names is pinned, and a caller that passed those two by position must get a TypeError, not another keyword)
         lib = _lib.lib()
         given = dict(prioritized=prioritized, rollout=rollout, td_priority=td_priority, prioritized_batch=prioritized_batch, wide_batch=wide_batch,
-                     dueling_batch=dueling_batch)
+                     dueling_batch=dueling_batch, rollout_batch=rollout_batch)
         given = {k: v for k, v in given.items() if (v is not None if k.endswith("_batch") else v)}
         # every keyword is an explicit opt-in: entry_of() and ENTRY_BY_METHOD keep answering what they answered
-        spec = next((e for e in reversed(ENTRIES) if e.keyword in given), None)
+        spec = next((e for e in reversed(ALL_ENTRIES) if e.keyword in given), None)
         if spec is None:
             spec = ENTRY.get(entry_of(brain.kind))
             if spec is None:

@@ -490,7 +490,10 @@ class DeviceWorlds:
         (rl_learn_rollout) -- the window is the rows appended to a ring since the last call (the whole ring once that is more than it
         holds); each of the n_steps * batch draws takes a window row uniformly, with replacement, by a key of the rows' content: the same
         rows whatever slots they sit in.  Leaves the number of rows of the window in learner.fresh (an empty one: the following learn()
-        makes no update) and moves learner.seen up.  Device int32 [len(learners), n_steps, batch], queued on the current stream."""
+        makes no update) and moves learner.seen up.  Device int32 [len(learners), n_steps, batch], queued on the current stream.
+        A list of wide PPO learners (DeviceLearner(..., rollout=True, rollout_batch=B)) goes to rl_learn_rollout_wide: the same two launches
+        and the same arithmetic for rollouts of up to 2048 rows (B <= 32: rl_learn_rollout's table).  The learners of a call are all of the
+        one kind or all of the other."""
         return self._draw_side("draw_rollout", learners, n_steps, _lib.Ppo, "a PPO one (DeviceLearner(..., rollout=True))")
 
     def draw_td(self, learners, n_steps):
@@ -609,7 +612,10 @@ class DeviceWorlds:
         rows, 64-row tiles side by side with the advantage mean of the whole batch, 3 n_steps + 3 launches; one batch per call; `slots`
         from draw_slots() / draw_slots_rank() or None), a list of wide prioritised PERD3QN learners (DeviceLearner(..., prioritized=True,
         prioritized_batch=B)) to rl_learn_prioritized_wide (that tiled update plus the priorities of all B rows and their maximum, 3 n_steps
-        + 3 launches; one batch per call; `slots` must come from draw_prioritized()).  The
+        + 3 launches; one batch per call; `slots` must come from draw_prioritized()), a list of wide PPO learners (DeviceLearner(...,
+        rollout=True, rollout_batch=B)) to rl_learn_ppo_wide (PPO.learn() on rollouts of B <= 2048 rows, 32-row tiles side by side with one
+        GAE recursion over the whole rollout, 3 n_steps k_epoch + 3 launches with the largest k_epoch of the call; one batch per call;
+        `slots` from draw_rollout(), or the caller's own rows with gate=False).  The
         learners of one call must all belong to one entry point: ValueError otherwise."""
         if not learners:
             return
@@ -617,7 +623,7 @@ class DeviceWorlds:
         entries = {l.entry for l in learners}
         if len(entries) != 1:
             raise ValueError("learn(): the learners of a call must be of one kind (one entry point), got %s" % sorted(entries))
-        spec = learners[0].spec   # (the row of learn.ENTRIES: every C signature is handle, learners, rings, [side structs], n, n_steps, slots, [work], stream)
+        spec = learners[0].spec   # (the row of learn.ALL_ENTRIES: every C signature is handle, learners, rings, [side structs], n, n_steps, slots, [work], stream)
         if n > _lib.MAX_CAPTURE_BRAINS:
             raise ValueError("learn(): at most %d learners per call (got %d)" % (_lib.MAX_CAPTURE_BRAINS, n))
         arr = (_lib.Learner * n)(*[l.struct() for l in learners])
@@ -634,7 +640,7 @@ class DeviceWorlds:
         work = [(C.c_void_p * n)(*[l.work.data_ptr() for l in learners])] if spec.narrow else []
         _lib.check(getattr(self.lib, spec.name)(self.handle, arr, rings, *sides, n, int(n_steps), _ptr(slots), *work, self._stream()), spec.name)
         self._learn_keep = slots   # (the launch reads the table asynchronously)
-        self.launches += spec.launches(int(n_steps))
+        self.launches += spec.launches(int(n_steps), max(l.k_epoch for l in learners)) if spec.per_epoch else spec.launches(int(n_steps))
 
     def export_learners(self, learners, out=None):
         """The learners' state as ONE flat float32 row on the device (rl_learn_export, one launch, queued on the current stream): learner i's
