@@ -1,6 +1,8 @@
 """TEST INFRASTRUCTURE ONLY -- generates tests/golden/*.npz from the REAL reference (build container only).
 
-    python oracle/gen_golden.py
+    python oracle/gen_golden.py                    every fixture
+    python oracle/gen_golden.py --extras-only      resets.npz and the two key lists only
+    python oracle/gen_golden.py --shapes-only      the four world-shape traces only (shape_traces), the other files left as they are
 
 Fixtures are data only: inputs (initial world, per-tick actions, RNG tape) and the outputs the reference produced
 (post-step / post-update worlds, rewards, observations; network outputs for repo-generated weights).  No reference
@@ -276,11 +278,23 @@ def state_dict_keys():
     print("wrote %s" % path)
 
 
+def shape_traces():
+    """The narrowest, longest and fullest grids (tests/world_shape_cases.py): 8-bit coordinates up to 254 on either axis, both sides below
+    the 7-wide window, 4,095 cells with an odd width."""
+    trace_case("long255x16", 19, 30, width=255, height=16, fill=100)
+    trace_case("tall16x255_nonstatic", 20, 30, width=16, height=255, fill=100, static=False, n_brains=3)
+    trace_case("tiny4x6_nonstatic", 21, 60, width=4, height=6, fill=8, max_agents=8, static=False)
+    trace_case("odd65x63_attack", 22, 12, width=65, height=63, fill=250, max_agents=250, p_attack=0.5)
+
+
 def main():
     os.makedirs(OUT_DIR, exist_ok=True)
     if "--extras-only" in sys.argv:
         reset_vectors()
         state_dict_keys()
+        return
+    if "--shapes-only" in sys.argv:
+        shape_traces()
         return
     trace_case("natural_static", 11, 120, n_brains=3)
     trace_case("natural_nonstatic", 12, 150, n_brains=2, static=False)
@@ -290,6 +304,7 @@ def main():
     trace_case("movers250", 16, 10, fill=250, max_agents=300, p_attack=0.0)
     trace_case("small7x5", 17, 60, width=7, height=5, fill=12, max_agents=20)
     trace_case("rect30x20_limit", 18, 40, width=30, height=20, fill=60, limit=True, incentive=False, max_agents=80)
+    shape_traces()
     micro_cases()
     model_vectors()
     reset_vectors()

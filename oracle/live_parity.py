@@ -3,7 +3,7 @@
     python oracle/live_parity.py [--quick]
 
 Runs the imported reference (oracle/ref_harness.py) tick by tick on randomised worlds -- natural populations, dense
-100/200/300-agent worlds, small grids, static and non-static families -- feeding the recorded actions and RNG tape to
+100/200/300-agent worlds, small grids, grids of 3 .. 255 cells a side, static and non-static families -- feeding the recorded actions and RNG tape to
 the oracle, and requires bit-identical integer state, float32-identical observations and rewards, after every step
 and every update_env.  The oracle is NOT re-synchronised between ticks: it free-runs from the initial snapshot.
 """
@@ -122,6 +122,17 @@ def main():
         cases.append(dict(name="rect30x20-limit-%d" % s, seed=700 + s, ticks=60, width=30, height=20, fill=60,
                           limit=True, incentive=False, max_agents=80))
         cases.append(dict(name="movers-only-%d" % s, seed=800 + s, ticks=30, fill=250, max_agents=300, p_attack=0.0))
+    # the narrowest, longest and fullest grids (tests/world_shape_cases.py): coordinates up to 254 on either axis, sides below the 7-wide
+    # window, 4,095 cells with an odd width
+    for s in range(scale):
+        cases.append(dict(name="long255x16-%d" % s, seed=900 + s, ticks=40, width=255, height=16, fill=100))
+        cases.append(dict(name="tall16x255-nonstatic-%d" % s, seed=910 + s, ticks=40, width=16, height=255, fill=100, static=False, n_brains=3))
+        cases.append(dict(name="thin3x255-%d" % s, seed=920 + s, ticks=60, width=3, height=255, fill=60, max_agents=60))
+        cases.append(dict(name="flat255x3-nonstatic-%d" % s, seed=930 + s, ticks=60, width=255, height=3, fill=60, max_agents=60, static=False))
+        cases.append(dict(name="min3x3-%d" % s, seed=940 + s, ticks=60, width=3, height=3, fill=4, max_agents=4))
+        cases.append(dict(name="tiny4x6-nonstatic-%d" % s, seed=950 + s, ticks=60, width=4, height=6, fill=8, max_agents=8, static=False))
+        cases.append(dict(name="tiny6x4-attack-%d" % s, seed=960 + s, ticks=60, width=6, height=4, fill=8, max_agents=8, p_attack=0.6))
+        cases.append(dict(name="odd65x63-attack-%d" % s, seed=970 + s, ticks=30, width=65, height=63, fill=300, max_agents=300, p_attack=0.5))
     for c in cases:
         st = run_case(**c)
         for k in total:
