@@ -153,7 +153,24 @@ typedef struct {
 
 /* Replay ring of ONE brain (caller-owned device buffers): what Agent.learn hands to brain.learn each tick
  * (World/entities.py:194-208 -> DQN.py:73-84, D3QN.py:94-96, PERD3QN.py:91-92,117-125, PPO.py:69-76), stored in
- * slot (count % capacity) in Agent.learn call order per world. */
+ * slot (count % capacity) in Agent.learn call order per world.
+ *   The contract of the two writers (rl_capture_transitions, and rl_run_ex with `replays`):
+ *   count     *count after a launch == *count before + the rows appended.  It only grows (64 bits); the slot is count mod capacity.
+ *   one world row n of a launch's call-order list sits in slot (count0 + n) % capacity, later rows over earlier ones: the reference's
+ *             deque(maxlen=capacity).
+ *   worlds    every (world, tick) list is reserved by ONE atomic on *count and is one contiguous run of slots in call order; the worlds'
+ *             runs of a tick follow each other in the order their workgroups reach the counter.  A launch that appends at most
+ *             `capacity` rows leaves every slot outside [count0, count0 + rows) % capacity untouched.
+ *   floor     capacity >= n_worlds * slot_cap, the most rows ONE tick of all worlds can append to one ring: both entry points refuse a
+ *             smaller ring (RL_E_INVALID naming the ring, its capacity and the floor) before anything is launched.  Below the floor two
+ *             rows of one tick map to the same slot; they are written by different threads (across worlds: different workgroups), each
+ *             row in parts, and nothing orders those writes -- the slot could end as the state of one transition with the reward or
+ *             state_prime of another.
+ *   assumed   the floor keeps the rows of ONE tick apart, not those of different ticks: inside a multi-tick launch the worlds are not in
+ *             lockstep, and a world that has reserved its slots must finish writing that tick's rows before the other worlds have
+ *             appended a whole further ring's worth of rows (capacity rows beyond its reservation) and reach the same slots again.  The
+ *             kernel does not guarantee that; a ring of several ticks' rows (the reference's sizes: 10,000 and up) makes it a matter of
+ *             one world stalling for that many ticks of all the others. */
 typedef struct {
     float* state;                /* [capacity][153] observation the policy read before the step */
     float* state_prime;          /* [capacity][153] post-step observation */
@@ -258,7 +275,8 @@ typedef struct {
                                       * inside the kernel arguments (copied during the call) -- a short launch then waits for no upload */
     const rl_replay* replays;        /* host array [n_brains] or NULL: every tick's transitions are appended to the brains' replay rings
                                       * inside the launch -- what rl_capture_transitions does after a stand-alone tick (trainer.py:95-96,
-                                      * entities.py:194-208); the rings' order is Agent.learn call order per world, worlds interleaved */
+                                      * entities.py:194-208); the rings' order is Agent.learn call order per world, worlds interleaved;
+                                      * a ring below n_worlds * slot_cap rows is RL_E_INVALID (rl_replay: floor) */
     float* policy_out;               /* device [R][cap][8] or NULL: the policy's outputs (Q values / PPO probabilities) of the LAST tick,
                                       * indexed like `actions`; with `replays`, rl_replay.prob gets the taken action's entry every tick */
 } rl_run_opts;
@@ -275,7 +293,8 @@ int rl_run_ex(rl_world* h, const rl_brain* brains, int n_brains, int n_ticks, in
  *   actions    [R][cap]      this tick's actions (pre-step list order)
  *   policy_out [R][cap][8]   optional rl_policy_act outputs of this tick
  *   step       outputs of this tick's rl_step / rl_tick; needs reward, done, src, obs, n_post, age, brain
- *   replays    host array of n_brains rings (n_brains <= RL_MAX_CAPTURE_BRAINS) */
+ *   replays    host array of n_brains rings (n_brains <= RL_MAX_CAPTURE_BRAINS), each of at least n_worlds * slot_cap rows (rl_replay:
+ *              floor; a smaller one is RL_E_INVALID naming it) */
 int rl_capture_transitions(rl_world* h, const float* state, const int8_t* actions, const float* policy_out,
                            const rl_step_out* step, const rl_replay* replays, int n_brains, void* stream);
 

@@ -395,7 +395,16 @@ class Environment:
             # a D3QN or prioritised PERD3QN learner's ring holds its brain's `capacity` rows (D3QN.py:62, PERD3QN.py:49, 55: 10,000), a
             # PERDQN learner's its brain's memory_size (20,000); every other ring stays DQN.py:15's
             rows = [int(getattr(b, plan[k].ring_rows)) if k in plan and plan[k].ring_rows else BUFFER_LIMIT for k, b in enumerate(brains)]
-            self.worlds.enable_capture(rows if any(e.ring_rows for e in plan.values()) else BUFFER_LIMIT, **prob)
+            # ... and none is smaller than what one tick of all worlds can append to it (n_worlds * slot_cap, the floor of rl_replay: below it
+            # two rows of one tick would share a slot, written in no order): a ring below the floor is raised to it, and the learner's
+            # size gate and draws then see that many rows.  ring_rows says what was chosen; with nothing below the floor the call is the
+            # one it always was
+            floor = int(n_worlds) * _lib.slot_cap_for(max_agents)
+            self.ring_floor, self.ring_rows = floor, [max(r, floor) for r in rows]
+            if self.ring_rows != rows:
+                self.worlds.enable_capture(self.ring_rows, **prob)
+            else:
+                self.worlds.enable_capture(rows if any(e.ring_rows for e in plan.values()) else BUFFER_LIMIT, **prob)
             for k, e in plan.items():   # (learn_batch: the wide entry in the narrow one's place, through its own keyword on top)
                 kw = {e.keyword: True} if e.keyword else {}
                 if self.learn_batch_of.get(e.method) is not None:

@@ -348,6 +348,25 @@ int rl_run_supported(const rl_world* h, const rl_brain* brains, int n_brains)
     return rl_world_run_supported(h, brains, n_brains);
 }
 
+// The rings transition capture appends to (rl_run_ex with `replays`, rl_capture_transitions), checked before anything is launched: complete,
+// and no smaller than the most rows ONE tick of all worlds can append to one ring -- n_worlds * slot_cap, the floor of rl_replay
+// (include/reinlife_hip.h).  Below it two rows of one tick can map to the same slot, and nothing in either kernel orders their writes.
+static int check_capture_rings(const rl_world* h, const rl_replay* replays, int n_brains, const char* who)
+{
+    const long long floor_rows = (long long)h->cfg.n_worlds * h->cfg.slot_cap;
+    for (int i = 0; i < n_brains; ++i) {
+        const rl_replay& r = replays[i];
+        if (!r.state || !r.state_prime || !r.action || !r.reward || !r.done || !r.age || !r.count || r.capacity < 1) { rl_set_error("%s: replay %d incomplete", who, i); return RL_E_INVALID; }
+        if (r.capacity < floor_rows) {
+            rl_set_error("%s: replay %d: capacity %lld is below the floor of %lld rows (n_worlds %d x slot_cap %d, the most rows one tick of all worlds can "
+                         "append to one ring: a smaller ring would take two rows of one tick in one slot, written in no order)",
+                         who, i, (long long)r.capacity, floor_rows, h->cfg.n_worlds, h->cfg.slot_cap);
+            return RL_E_INVALID;
+        }
+    }
+    return RL_OK;
+}
+
 int rl_run_ex(rl_world* h, const rl_brain* brains, int n_brains, int n_ticks, int8_t* actions, const rl_step_out* sout,
               float* const obs[2], int first_obs, int16_t* update_src, const rl_run_opts* opts, void* stream)
 {
@@ -359,12 +378,8 @@ int rl_run_ex(rl_world* h, const rl_brain* brains, int n_brains, int n_ticks, in
     if (n_ticks < 0 || (first_obs != 0 && first_obs != 1)) { rl_set_error("rl_run: bad n_ticks / first_obs"); return RL_E_INVALID; }
     if (opts->threshold >= 0 && (opts->n_agents < 0 || opts->n_agents > h->cfg.slot_cap || opts->n_agents > h->cells)) { rl_set_error("rl_run: bad refill arguments"); return RL_E_INVALID; }
     if (int rc = check_step_out(sout, "rl_run")) return rc;
-    if (opts->replays) {
-        for (int i = 0; i < n_brains; ++i) {
-            const rl_replay& r = opts->replays[i];
-            if (!r.state || !r.state_prime || !r.action || !r.reward || !r.done || !r.age || !r.count || r.capacity < 1) { rl_set_error("rl_run: replay %d incomplete", i); return RL_E_INVALID; }
-        }
-    }
+    if (opts->replays)
+        if (int rc = check_capture_rings(h, opts->replays, n_brains, "rl_run")) return rc;
     for (int b = 0; b < n_brains; ++b)
         if (brains[b].kind < RL_DQN || brains[b].kind > RL_PERDQN || !brains[b].packed) { rl_set_error("rl_run: brain %d invalid", b); return RL_E_INVALID; }
     if (n_ticks == 0) return RL_OK;
@@ -391,8 +406,7 @@ int rl_capture_transitions(rl_world* h, const float* state, const int8_t* action
     if (n_brains != h->cfg.n_brains || n_brains > RL_MAX_CAPTURE_BRAINS) { rl_set_error("rl_capture_transitions: n_brains %d (config %d, max %d)", n_brains, h->cfg.n_brains, RL_MAX_CAPTURE_BRAINS); return RL_E_INVALID; }
     if (!step->reward || !step->done || !step->src || !step->obs || !step->n_post || !step->age || !step->brain) { rl_set_error("rl_capture_transitions: step outputs reward/done/src/obs/n_post/age/brain are required"); return RL_E_INVALID; }
     if (h->cfg.slot_cap > 4096) { rl_set_error("rl_capture_transitions: slot_cap > 4096"); return RL_E_UNSUPPORTED; }
-    for (int i = 0; i < n_brains; ++i)
-        if (!replays[i].state || !replays[i].state_prime || !replays[i].action || !replays[i].reward || !replays[i].done || !replays[i].age || !replays[i].count || replays[i].capacity < 1) { rl_set_error("rl_capture_transitions: replay %d incomplete", i); return RL_E_INVALID; }
+    if (int rc = check_capture_rings(h, replays, n_brains, "rl_capture_transitions")) return rc;
     return rl_world_launch_capture(h, state, actions, policy_out, step, replays, n_brains, (hipStream_t)stream);
 }
 

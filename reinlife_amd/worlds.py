@@ -385,15 +385,26 @@ class DeviceWorlds:
         self.tracking = bool(on)
         self._build_step_out()
 
+    def capture_floor(self):
+        """The smallest replay ring transition capture accepts for this handle: n_worlds * slot_cap rows."""
+        return self.R * self.cap
+
     def enable_capture(self, capacity, with_prob=False):
         """Allocate one replay ring per brain (rl_replay): filled by capture_transitions() after a stand-alone tick, or by run() inside
-        the multi-tick launch (every tick of it).  capacity: one number for all rings, or one per brain."""
-        self._capture_prob = bool(with_prob)
-        self.replays = []
-        arr = (_lib.Replay * self.n_brains)()
+        the multi-tick launch (every tick of it).  capacity: one number for all rings, or one per brain -- each at least capture_floor(),
+        n_worlds * slot_cap rows: what one tick of all worlds can append to one ring (rl_replay in include/reinlife_hip.h; a smaller ring
+        would take two rows of one tick in one slot, and nothing orders their writes)."""
         caps = [int(capacity)] * self.n_brains if np.isscalar(capacity) else [int(c) for c in capacity]
         if len(caps) != self.n_brains or min(caps) < 1:
             raise ValueError("enable_capture(): capacity must be one positive number or one per brain (%d brains), got %r" % (self.n_brains, capacity))
+        floor = self.capture_floor()
+        for b, c in enumerate(caps):
+            if c < floor:
+                raise ValueError("enable_capture(): ring %d: capacity %d is below the floor of %d rows (n_worlds %d x slot_cap %d, the most rows one "
+                                 "tick of all worlds can append to one ring)" % (b, c, floor, self.R, self.cap))
+        self._capture_prob = bool(with_prob)
+        self.replays = []
+        arr = (_lib.Replay * self.n_brains)()
         for b, capacity in enumerate(caps):
             r = {"state": torch.zeros((capacity, _lib.OBS_DIM), dtype=torch.float32, device=self.device),
                  "state_prime": torch.zeros((capacity, _lib.OBS_DIM), dtype=torch.float32, device=self.device),
