@@ -1020,8 +1020,55 @@ __device__ inline bool policy_tile1s(const IO& io, int lane, int role = 0, const
         row = io.row0 + tr.k; key_index = (uint32_t)tr.k;
         x_lds_off = (io.x_lds_off >= 0 && tr.k < io.xrows) ? io.x_lds_off + tr.k * io.x_stride * (int)sizeof(float) : -1;
     } else { row = io.row; key_index = io.key_index; x_lds_off = io.x_lds_off; }
+    [[maybe_unused]] bool all_mirrored = false;   // TileRef: every row of the tile comes from the LDS mirror (wave-uniform)
     {
         const int64_t rbase = row * RL_OBS_DIM;
+        if constexpr (kRef) {
+            // k_run's certified tile: ONE wave-uniform branch between the two sources, each arm free of branches.  As the two arms of a per-lane
+            // if / else (below: the other tiles) the LDS reads write the registers the memory arm's buffer loads write, and the compiler
+            // guards each ds_read_b128 with an s_waitcnt vmcnt(19 .. 0) against those loads -- skipped by execz on the hot path, where the
+            // waits then count w1.start()'s twelve fragments: the row reads, the row maximum, the scale and the first split stood behind the
+            // arrival of the whole ring start instead of in the shadow of its L2 round trip.  (A uniform block NEXT to the per-lane branch
+            // does not help: the structurizer lays it out behind that branch's join and it inherits the same waits.)
+            //   every row of the tile mirrored (k_run's hot path)  ->  twenty ds_read_b128 and nothing else.  Chunk 9 of the upper half is the
+            //       16-byte unit at float 152 as it lies (inside the row's stride of 164 floats): its one real input is .x there, .w of the
+            //       unit at 149 that the memory arm reads (the fix-up below takes the one or the other);
+            //   else  ->  EVERY lane reads its row from memory, the lanes whose rows are mirrored too: the same float32 values --
+            //       write_observations stores every row, mirrored or not, and a world with a row beyond the mirror (n > xrows) has drained
+            //       its stores to L2 before a tile starts (recycle_world's drain_stores; a first tick with n > xrows does not preload the mirror).
+            // (the test goes through an opaque SGPR, so that the branch is a scalar one whatever the compiler makes of the ballot)
+            const unsigned long long mem_lanes = __builtin_amdgcn_ballot_w64(x_lds_off < 0);
+            int from_memory = __builtin_amdgcn_readfirstlane((int)((unsigned)mem_lanes | (unsigned)(mem_lanes >> 32)));
+            asm volatile("" : "+s"(from_memory));
+            all_mirrored = from_memory == 0;
+            if (all_mirrored) {
+                const float* xr = (const float*)(rl_dyn_lds + x_lds_off) + 8 * h;
+#pragma unroll
+                for (int c = 0; c < kInChunks - 1; ++c)
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) X[c][q] = *(const f32x4*)(xr + 16 * c + 4 * q);
+                X[kInChunks - 1][0] = *(const f32x4*)(xr + 16 * (kInChunks - 1));   // h == 0: floats 144 .. 147; h == 1: 152 .. 155
+                X[kInChunks - 1][1] = *(const f32x4*)(xr + 16 * (kInChunks - 1) + 4 - 8 * h);   // floats 148 .. 151 (h == 1: not used)
+            } else {
+#pragma unroll
+                for (int c = 0; c < kInChunks; ++c)
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        const int k0 = (c == kInChunks - 1 && h == 1) ? 149 : 16 * c + 8 * h + 4 * q;
+                        if (COHERENT) {
+                            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)io.obs, 0, 0x7fffffff, 0x00027000);
+                            X[c][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((rbase + k0) * 4), 0, 16 /* sc1 */));
+                        } else
+                            X[c][q] = *(const f32x4u*)(io.obs + rbase + k0);
+                    }
+                // The memory arm ends with its rows ARRIVED (an empty asm that reads them: the compiler waits in front of it).  The emitted
+                // code keeps a static fall-through from this arm into the mirror block (the arm leaves through s_cbranch_execnz), and whatever
+                // is still in flight here the compiler guards against there -- an s_waitcnt vmcnt(0) in front of the first ds_read_b128, for
+                // one address register.  The rows are consumed next anyway (row maximum): the arm loses the Philox block's overlap, nothing else.
+#pragma unroll
+                for (int c = 0; c < kInChunks; ++c) asm volatile("" :: "v"(X[c][0]), "v"(X[c][1]));
+            }
+        } else {
         if (x_lds_off >= 0) {
             const float* xr = (const float*)(rl_dyn_lds + x_lds_off);
 #pragma unroll
@@ -1043,10 +1090,11 @@ __device__ inline bool policy_tile1s(const IO& io, int lane, int role = 0, const
                 } else
                     X[c][q] = *(const f32x4u*)(io.obs + rbase + k0);
             }
+        }   // (not a TileRef tile)
     }
     rl_u4 draw = {0u, 0u, 0u, 0u};
     if ((!PAIR || role == 0) && io.actions && io.eps > 0.0f) draw = rl_philox4x32(io.seed, io.key_epoch, io.key_world, io.key_tick, RL_SITE_ACT, key_index);
-    if (h == 1) { X[kInChunks - 1][0] = f32x4{X[kInChunks - 1][0].w, 0.0f, 0.0f, 0.0f}; X[kInChunks - 1][1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
+    if (h == 1) { X[kInChunks - 1][0] = f32x4{(kRef && all_mirrored) ? X[kInChunks - 1][0].x : X[kInChunks - 1][0].w, 0.0f, 0.0f, 0.0f}; X[kInChunks - 1][1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
     // the row's scale: known without looking when the rows are the world kernels' own (RL_XF_SCALE, see in_chunk_class) -- else from the row's
     // largest magnitude: four independent chains of max3(m, |a|, |b|), 40 instructions (the compiler's tree over fabsf / fmaxf is 92, and
     // ONE chain of 40 is slower than that tree: a dependent VALU instruction costs a lone wave more than its issue slot)

@@ -226,6 +226,9 @@ __device__ inline RecycleRegs recycle_read(Smem& s, int n)
 // launch) -- and (b) what a tile WRITES, s.action[k] and the action bytes in memory, nobody writes or reads in here (`open`).  Nothing
 // aliases the mirror any more (the pair tiles' exchange buffers did: the full path, which keeps its two barriers inside the tile, both
 // behind every wave's row reads).  The fallback of a certified tile reads the same rows again before its wave reaches the closing barrier.
+// A certified tile with ANY row beyond the mirror reads ALL its rows from memory, the mirrored ones too (policy_tile1s: one uniform branch
+// between the sources): such a tile exists only where n > xrows, and that is where `drain_stores` holds below -- every wave's row stores
+// of this tick have reached L2 and the barrier stays, so (a) covers those reads as it covers the rows beyond the mirror.
 #ifndef RL_SEAM_OPEN
 #define RL_SEAM_OPEN 1
 #endif
