@@ -27,6 +27,8 @@
  *   rl_learn_ppo       PPO.learn(): k_epoch full-batch Adam steps on a rollout of at most 32 rows (rl_learn_rollout draws it)
  *   rl_learn_ppo_wide  PPO.learn() on a rollout of up to 2048 rows, 32-row tiles side by side, ONE GAE recursion over the whole rollout
  *                      (rl_learn_rollout_wide draws it)
+ *   rl_learn_td_wide   PERDQNAgent.train_model() on a minibatch of up to 2048 rows, 64-row tiles side by side, the importance weights'
+ *                      minimum and mean over the whole batch from a pass of its own in front of every step's tiles
  *   rl_learn_dueling   D3QNAgent.train(): one minibatch update of the dueling network (MSE, Adam), batch up to 64
  *                      Models/D3QN.py:97-116, 148-165 (schedule and target copy of :118-126: the caller's)
  *
@@ -205,7 +207,7 @@ int rl_bind_state(rl_world* h, const rl_state* device_ptrs);
  *   3  a world's agent list outgrew slot_cap                                 detail: slots
  *   4  a taped produce_choice outside [0, RL_N_BEST)                         detail: value
  *   5  rl_render: a world id outside [0, n_worlds) ([1] = the id)            detail: frame index
- *   6  rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo / rl_learn_td: a minibatch slot outside [0, ring size) ([1] = brain index) detail: step, value */
+ *   6  rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo / rl_learn_td / rl_learn_td_wide: a minibatch slot outside [0, ring size) ([1] = brain index) detail: step, value */
 int rl_bind_error_flag(rl_world* h, int32_t* device_flag);
 
 /* tuning aid: device int64[32] receiving shader-clock stamps at the phase boundaries of world `world` (NULL = off) */
@@ -909,6 +911,62 @@ int rl_learn_td_stamp(rl_world* h, const rl_learner* learners, const rl_replay* 
  * Every older entry point and *_supported answer is unchanged by it (they refuse RL_PERDQN). */
 int rl_learn_td(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
                 const int32_t* slots, void* stream);
+/* THIS BUILD'S OWN -- the reference trains one world on ONE minibatch of 64 per train_model() (PERDQN.py:130-186).  rl_learn_td_wide is
+ * rl_learn_td on a minibatch of 1 .. RL_LEARN_TD_WIDE_MAX rows, computed in 64-row tiles with one 512-thread workgroup per (learner,
+ * tile).  The rows of a step meet in two scalars, p_min and mean(is_w), both over the WHOLE batch, and the tiles rewrite the priorities
+ * those are read from: so every step has a weights pass of its own in front of its tiles, and no workgroup reads a priority that a
+ * workgroup of the same launch can write. */
+#define RL_LEARN_TD_WIDE_MAX 2048
+/* the launches one rl_learn_td_wide call queues: check | per step: weights, tiles, update | target / counters / beta | pack */
+#define RL_LEARN_TD_WIDE_LAUNCHES(n_steps) (3 * (n_steps) + 3)
+/* 1 for the brain kinds rl_learn_td_wide trains (RL_PERDQN), 0 for the others */
+int rl_learn_td_wide_supported(int kind);
+/* The bytes of one learner's work buffer at `batch`: a 64-byte header, one partial gradient row of rl_policy_n_params floats per tile
+ * and the tiles' sums of td^2, T = ceil(batch / 64) tiles.  0, with rl_last_error set, for a kind rl_learn_td_wide does not train or a
+ * batch outside [1, RL_LEARN_TD_WIDE_MAX]. */
+size_t rl_learn_td_wide_work_bytes(int kind, int batch);
+/* rl_learn_td_draw (two launches) and rl_learn_td_draw_rank (RL_LEARN_PRIO_DRAW_RANK_LAUNCHES launches; stratified != 0 cuts the total
+ * into `batch` segments) for these learners: the same kernels and arithmetic with batch in [1, RL_LEARN_TD_WIDE_MAX], ONE batch for all
+ * learners of a call and n_steps in [1,65536].  Draw d = s * batch + j keeps its salt -- words 0-1 of rl_philox(seed, 0, i,
+ * (uint32)state[1], RL_SITE_LEARN_TD, d) -- so with batch <= 64 the tables are rl_learn_td_draw's and rl_learn_td_draw_rank's, slot for
+ * slot.  Validation is theirs with the batch limit and the one-batch rule (RL_E_INVALID naming both batches); rl_learn_td_draw and
+ * rl_learn_td_draw_rank keep their limit of 64 and their messages. */
+int rl_learn_td_wide_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
+                          int32_t* slots, void* stream);
+int rl_learn_td_wide_draw_rank(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
+                               int stratified, int32_t* const* order, double* const* cum, void* const* work, int32_t* slots, void* stream);
+/* PERDQNAgent.train_model() on wide minibatches for n_learners brains: RL_LEARN_TD_WIDE_LAUNCHES(n_steps) stream-ordered launches, no
+ * allocation, no host round trip, no cooperative launch, no float atomics, no workgroup that waits for another.
+ *   batch       learners[i].batch in [1, RL_LEARN_TD_WIDE_MAX], ONE batch B for all learners of a call; slots is device int32
+ *               [n_learners][n_steps][B], from rl_learn_td_wide_draw / rl_learn_td_wide_draw_rank (or the caller's)
+ *   work        host array [n_learners] of caller-owned device scratch of rl_learn_td_wide_work_bytes bytes each, 16-byte aligned.  It
+ *               needs no initialisation and holds nothing between calls
+ *   check       once: the size gate min(*count, capacity) > min_size; every slot of every step of a learner that trains is
+ *               range-checked against [0, size) before anything is written -- a bad one sets error-flag code 6 as rl_learn_td does
+ *               ([1] = brain index, [2] = step, [3] = the slot) and that learner leaves with NONE of its buffers written, priority and
+ *               beta included, while the others train; the counters as read at entry go into the work buffer's header
+ *   weights     per step, one workgroup per learner, finished before any tile of the step starts and started after every tile of the
+ *               previous step: beta = min(1, beta + beta_increment) in double; the step's B priorities as they stand; p_min by fminf
+ *               over the rows ascending; w_i = (float)pow((double)p_i / (double)p_min, -beta), each by its own thread, to
+ *               is_weight[s][0..B) when given; per tile the f32 sum of w, rows ascending; the tile sums added in double in tile order
+ *               from the additive identity (-0.0) and rounded to float once; mean_w = that * (1.0f / B)
+ *   tiles       per step, one workgroup per (learner, 64 rows): rl_learn_td's arithmetic thread for thread -- the target forward on s',
+ *               the eval forward on s, td = pred - target, row_g = mean_w * ((2 td) * (1 / B)) with B the whole batch; the row's own
+ *               tile writes priority[slot] = powf(fabsf(td) + prio_e, prio_a) (duplicated slots, also across tiles, carry equal bits:
+ *               no winner rule); the tile's f32 sum of td^2 and its partial gradient of all 14,536 parameters (f32 sums over the
+ *               tile's rows, ascending) go to the work buffer
+ *   update      per step, one thread per parameter: the tiles' partials added in tile order in double (from -0.0), rounded once, then
+ *               rl_learn_td's Adam update; grad[s] and loss[s] = mean_w * (sum_sq * (1 / B)) are written when given, sum_sq formed from
+ *               the tile sums as mean_w's sum is
+ *   afterwards  sync_target != 0: target <- params, also below the size gate; state[0] += updates made; state[1] += 1; *beta is written
+ *               iff the learner trained; `packed` is rewritten from the final params by rl_policy_pack_device's kernel
+ * With one tile (B <= 64) and the same slots every buffer -- params, target, adam_m, adam_v, state, packed, priority, beta, is_weight,
+ * loss, grad -- ends with rl_learn_td's bits: float -> double -> float is the identity.  Deterministic: the same bits in every run,
+ * whatever else is in the launch.  Validation is rl_learn_td's with these differences: batch in [1, RL_LEARN_TD_WIDE_MAX] and equal for
+ * all learners, n_steps in [1,65536], work and every work[i] non-null (RL_E_INVALID naming the argument); a kind that is not RL_PERDQN:
+ * RL_E_UNSUPPORTED naming the kind.  rl_learn_td keeps its limit of 64 and its messages. */
+int rl_learn_td_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
+                     const int32_t* slots, void* const* work, void* stream);
 
 /* ---- learning on several ranks: one merge of the learners per learning episode ------------------------------------- */
 /* THIS BUILD'S OWN -- the reference has no multi-process training.  Every rank trains its learners on its own rings exactly as a single

@@ -141,6 +141,16 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     in every run.  The draw is rl_learn_rollout_wide (the on-policy draw at that width: with replacement, by content key);
     rollout_steps, schedule, the empty-window gate, k_epoch, learning rate and learn_ranks are the PPO learners'; a call is
     2 + 3 rollout_steps k_epoch + 3 launches instead of 2 + 1.  {"PPO": 32} gives the learners that learn_rollout=True alone gives, bit for bit.
+    With learn_td_priority=True (and only then: without it the key stays unknown) the dict also takes "PERDQN" (this build's own -- the
+    reference's minibatch is 64 rows, PERDQN.py:130-186): every PERDQN learner trains through rl_learn_td_wide, train_model()'s update on a
+    minibatch of B rows in [1, 2048] computed in 64-row tiles side by side.  The importance weights (p_i / min_j p_j) ** -beta and their
+    mean run over the WHOLE batch, as Memory.sample() makes them: a pass of its own in front of every step's tiles takes the minimum and
+    the mean from the priorities as they stand, the tiles then rewrite the priority of every one of the B rows, and the tiles' gradients
+    are summed in tile order in double -- the same bits in every run.  The draw is rl_learn_td_wide_draw (the race draw at that width) or,
+    with learn_draw={"PERDQN": "rank"}, rl_learn_td_wide_draw_rank, stratified into B segments; learn_steps["PERDQN"], the train_start
+    gate, the target copy at every call, the epsilon decay, learn_td_stamp and learn_ranks are the PERDQN learners'; a call is
+    3 learn_steps["PERDQN"] + 3 launches instead of one.  {"PERDQN": 64} gives the learners that learn_td_priority=True alone gives, bit
+    for bit, priorities and beta included.
     learn_draw (default None: every run is launch for launch and bit for bit what it was; "rank" needs learn="device" and at least one
     brain of the learning kinds -- one that rl_learn, rl_learn_wide or rl_learn_dueling trains -- anything else is a ValueError before a
     device is touched): THIS BUILD'S OWN.  The DQN, wide DQN and D3QN learners' minibatches are then drawn by rl_learn_draw_rank instead of

@@ -209,6 +209,9 @@ class Environment:
         # minibatches of B rows (the prioritised draw at that width, the priorities of all B rows written); without it the key stays unknown.
         # With learn_rollout=True the dict also takes "PPO": every PPO learner trains through rl_learn_ppo_wide on rollouts of B rows (1 ..
         # 2048) in 32-row tiles, ONE GAE recursion over the whole rollout (the on-policy draw at that width); without it the key stays unknown.
+        # With learn_td_priority=True the dict also takes "PERDQN": every PERDQN learner trains through rl_learn_td_wide on minibatches of B
+        # rows (1 .. 2048) in 64-row tiles, the importance weights' minimum and mean taken over the whole batch (the reference's minibatch
+        # is 64, PERDQN.py); without it the key stays unknown.
         wide = {e.method: e for e in ENTRIES if e.narrow}   # the wide entry per brain method, a key of the dict only where its narrow entry is on
         self.learn_batch_of = dict.fromkeys(wide)
         if isinstance(learn_batch, dict):
@@ -217,7 +220,8 @@ class Environment:
             if unknown or not learn_batch:
                 raise ValueError("learn_batch as a dict takes the keys 'DQN' (rl_learn_wide) and 'D3QN' (rl_learn_dueling_wide)%s and at least one of them, got %r"
                                  % ((" and, with learn_prioritized=True, 'PERD3QN' (rl_learn_prioritized_wide)," if self.learn_prioritized else "")
-                                    + (" and, with learn_rollout=True, 'PPO' (rl_learn_ppo_wide)," if self.learn_rollout else ""), learn_batch))
+                                    + (" and, with learn_rollout=True, 'PPO' (rl_learn_ppo_wide)," if self.learn_rollout else "")
+                                    + (" and, with learn_td_priority=True, 'PERDQN' (rl_learn_td_wide)," if self.learn_td_priority else ""), learn_batch))
             for k, v in learn_batch.items():
                 limit = getattr(_lib, on[k].batch_max)
                 if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= limit:
@@ -793,6 +797,12 @@ class Environment:
                         "brain's train_start rows, loss scaled by the mean importance weight, target synced at every call, rows drawn with "
                         "probability priority / sum by content key with replacement -- independent draws, not the reference's stratified ones; "
                         "every new row gets the reference's one priority (0 + 0.01) ** 0.6; epsilon decays once per update"),
+        "rl_learn_td_wide": (True, "%(steps)d minibatch update(s) of batch %(wide)d (learn_batch) in 64-row tiles, the importance weights' "
+                             "minimum and mean taken over the whole batch and the priorities of all its rows rewritten, every %(every)d episodes "
+                             "once the ring holds the brain's train_start rows, loss scaled by the mean importance weight, target synced at every "
+                             "call, rows drawn with probability priority / sum by content key with replacement -- independent draws, not the "
+                             "reference's stratified ones; every new row gets the reference's one priority (0 + 0.01) ** 0.6; epsilon decays "
+                             "once per update"),
     }
     assert set(_NOTES) == set(ENTRY), "every row of learn.ALL_ENTRIES needs its note"
 
@@ -826,6 +836,7 @@ class Environment:
                                    ("PERDQN", "rl_learn_td_draw_rank", "stratified, draw j at (j + u_j) * total / batch: the reference's Memory.sample(), "
                                     "not the independent draws the note above states")):
             ks = [k for k in sorted(self.learners) if self.learners[k].spec.method == method]
+            entry = next((self.learners[k].spec.draw_rank for k in ks if self.learners[k].spec.draw_rank), entry)   # (a wide learner's own)
             if ks and self.learn_draw_of.get(method) == "rank":
                 note.append("the minibatches of brains %s drawn by prefix sum over content-key rank (learn_draw=%r, %s: the ring's rows sorted by "
                             "content key, their weights summed in that order in float64, every draw the smallest rank whose sum exceeds its target -- "
@@ -891,6 +902,13 @@ class Environment:
         tiles, one GAE recursion over the whole rollout) and are called in the PPO learners' place, the same way -- no gate but the empty
         window, `rollout_steps` rollouts, draw (rl_learn_rollout_wide, two launches) then learn (3 rollout_steps k_epoch + 3 launches
         instead of one) --; B = 32 draws rl_learn_rollout's rows and ends with rl_learn_ppo's bits.
+        learn_batch={"PERDQN": B} (with learn_td_priority=True): the PERDQN learners are wide ones (rl_learn_td_wide, minibatches of B rows
+        in 64-row tiles, the importance weights' minimum and mean over the whole batch from a pass in front of every step's tiles, the
+        priorities of all B rows rewritten) and are called in the PERDQN learners' place, the same way -- the train_start gate, the target
+        copy at every call, learn_steps["PERDQN"] steps, the stamp in front where learn_td_stamp asks for it, draw (rl_learn_td_wide_draw,
+        two launches, or with learn_draw={"PERDQN": "rank"} rl_learn_td_wide_draw_rank, eight launches, stratified at B) then learn
+        (3 learn_steps["PERDQN"] + 3 launches instead of one), the epsilon decay --; B = 64 draws rl_learn_td's rows and ends with its
+        bits, priorities and beta included.
         learn_draw="rank": the draw_slots calls above -- the DQN, wide DQN and D3QN learners' -- are draw_slots_rank calls (rl_learn_draw_rank,
         six launches instead of two: the rings' rows sorted by content key once, every draw an index into that order); the prioritised,
         rollout and PERDQN draws are what they are.

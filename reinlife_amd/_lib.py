@@ -97,6 +97,7 @@ LEARN_PRIO_DRAW_RANK_LAUNCHES = 8   # RL_LEARN_PRIO_DRAW_RANK_LAUNCHES: the laun
 LEARN_TD_STAMP_LAUNCHES = 2   # RL_LEARN_TD_STAMP_LAUNCHES: the launches of one rl_learn_td_stamp call
 PPO_ROLLOUT_MAX = 32   # RL_PPO_ROLLOUT_MAX: the rows of a rollout at most (rl_learn_ppo)
 LEARN_PPO_WIDE_MAX = 2048   # RL_LEARN_PPO_WIDE_MAX: the rows of a rollout at most (rl_learn_ppo_wide)
+LEARN_TD_WIDE_MAX = 2048   # RL_LEARN_TD_WIDE_MAX: the rows of a minibatch at most (rl_learn_td_wide)
 
 
 class Brain(C.Structure):
@@ -168,6 +169,11 @@ ABI = [
     ("rl_learn_td_draw_rank", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),
     ("rl_learn_td_stamp", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, _P]),
     ("rl_learn_td", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_td_wide_supported", C.c_int, [C.c_int]),
+    ("rl_learn_td_wide_work_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("rl_learn_td_wide_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_td_wide_draw_rank", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),
+    ("rl_learn_td_wide", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, C.POINTER(_P), _P]),
     ("rl_learn_merge_floats", C.c_int64, [C.c_int]),
     ("rl_learn_export", C.c_int, [_P, C.POINTER(Learner), C.c_int, _P, _P]),
     ("rl_learn_merge", C.c_int, [_P, C.POINTER(Learner), C.c_int, _P, C.c_int, C.c_int64, _P]),

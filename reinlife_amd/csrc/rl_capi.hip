@@ -7,7 +7,7 @@
 
 #include "rl_common.h"
 
-// implemented in rl_world.hip / rl_policy.hip / rl_render.hip / rl_learn.hip / rl_learn_dueling.hip / rl_learn_prio.hip / rl_learn_td.hip / rl_learn_merge.hip / rl_learn_wide.hip / rl_learn_dueling_wide.hip (also rl_learn_prioritized_wide) / rl_learn_ppo_wide.hip
+// implemented in rl_world.hip / rl_policy.hip / rl_render.hip / rl_learn.hip / rl_learn_dueling.hip / rl_learn_prio.hip / rl_learn_td.hip / rl_learn_merge.hip / rl_learn_wide.hip / rl_learn_dueling_wide.hip (also rl_learn_prioritized_wide) / rl_learn_ppo_wide.hip / rl_learn_td_wide.hip
 size_t rl_world_smem_bytes(int cpad, int cap, int hash, int plane_stride, int height);
 int rl_world_block();
 int rl_world_launch_step(rl_world*, const int8_t*, const rl_tape*, const rl_step_out*, hipStream_t);
@@ -53,6 +53,11 @@ int rl_learn_td_supported_impl(int);
 int rl_learn_td_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_tdprio*, int, int, const int32_t*, hipStream_t);
 int rl_learn_td_draw_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_tdprio*, int, int, int32_t*, hipStream_t);
 int rl_learn_td_stamp_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_tdprio*, int, hipStream_t);
+int rl_learn_td_wide_supported_impl(int);
+size_t rl_learn_td_wide_work_bytes_impl(int);
+int rl_learn_td_wide_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_tdprio*, int, int, const int32_t*, void* const*, hipStream_t);
+int rl_learn_td_wide_draw_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_tdprio*, int, int, int32_t*, hipStream_t);
+int rl_learn_td_wide_draw_rank_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_tdprio*, int, int, int, int32_t* const*, double* const*, void* const*, int32_t*, hipStream_t);
 int rl_learn_ppo_supported_impl(int);
 int rl_learn_ppo_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, const int32_t*, hipStream_t);
 int rl_learn_rollout_launch(rl_world*, const rl_learner*, const rl_replay*, const rl_ppo*, int, int, int32_t*, hipStream_t);
@@ -825,29 +830,35 @@ int rl_render(rl_world* h, const rl_render_style* style, const int32_t* worlds, 
 int rl_learn_td_supported(int kind) { return rl_learn_td_supported_impl(kind); }
 
 // what rl_learn_td and rl_learn_td_draw ask of their common arguments (`draw`: the draw also needs the rings' age column and the keys
-// scratch of rl_tdprio; the update needs the learner's buffers and beta)
+// scratch of rl_tdprio; the update needs the learner's buffers and beta).  The wide entries (rl_learn_td_wide, rl_learn_td_wide_draw,
+// rl_learn_td_wide_draw_rank) ask the same with their own batch limit, ONE batch for all learners of a call and n_steps up to 65536:
+// `max_batch`, `one_batch`, the name of the *_supported answer and of the draw.
 static int check_td(const char* who, bool draw, rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds,
-                    int n_learners, int n_steps, const void* slots)
+                    int n_learners, int n_steps, const void* slots, int max_batch = 64, bool one_batch = false,
+                    const char* supported = "rl_learn_td_supported", const char* drawn_by = "rl_learn_td_draw")
 {
     if (!h) { rl_set_error("%s: null handle", who); return RL_E_INVALID; }
     if (!learners || !rings || !tds) { rl_set_error("%s: null learners / rings / tds", who); return RL_E_INVALID; }
     if (n_learners < 1 || n_learners > RL_MAX_CAPTURE_BRAINS) { rl_set_error("%s: n_learners must be in [1,%d] (got %d)", who, RL_MAX_CAPTURE_BRAINS, n_learners); return RL_E_INVALID; }
     if (n_steps < 1) { rl_set_error("%s: n_steps must be >= 1 (got %d)", who, n_steps); return RL_E_INVALID; }
+    if (one_batch && n_steps > 65536) { rl_set_error("%s: n_steps must be in [1,65536] (got %d)", who, n_steps); return RL_E_INVALID; }
     if (!slots) {
-        rl_set_error(draw ? "%s: slots must not be null" : "%s: slots must not be null -- the minibatches of a prioritised memory are drawn by rl_learn_td_draw", who);
+        if (draw) rl_set_error("%s: slots must not be null", who);
+        else rl_set_error("%s: slots must not be null -- the minibatches of a prioritised memory are drawn by %s", who, drawn_by);
         return RL_E_INVALID;
     }
     for (int i = 0; i < n_learners; ++i) {
         const rl_learner& l = learners[i];
         const rl_replay& r = rings[i];
         const rl_tdprio& p = tds[i];
-        if (!rl_learn_td_supported_impl(l.kind)) { rl_set_error("%s: learner %d has brain kind %d; this entry point trains RL_PERDQN (4) only (rl_learn_td_supported)", who, i, l.kind); return RL_E_UNSUPPORTED; }
+        if (!rl_learn_td_supported_impl(l.kind)) { rl_set_error("%s: learner %d has brain kind %d; this entry point trains RL_PERDQN (4) only (%s)", who, i, l.kind, supported); return RL_E_UNSUPPORTED; }
         if (draw) {
             if (!l.state) { rl_set_error("%s: learner %d: state must not be null", who, i); return RL_E_INVALID; }
         } else if (!l.params || !l.target || !l.adam_m || !l.adam_v || !l.state || !l.packed) {
             rl_set_error("%s: learner %d: params / target / adam_m / adam_v / state / packed must not be null", who, i); return RL_E_INVALID;
         }
-        if (l.batch < 1 || l.batch > 64) { rl_set_error("%s: learner %d: batch must be in [1,64] (got %d)", who, i, l.batch); return RL_E_INVALID; }
+        if (l.batch < 1 || l.batch > max_batch) { rl_set_error("%s: learner %d: batch must be in [1,%d] (got %d)", who, i, max_batch, l.batch); return RL_E_INVALID; }
+        if (one_batch && l.batch != learners[0].batch) { rl_set_error("%s: learner %d: batch %d differs from learner 0's %d (the learners of a call share one batch)", who, i, l.batch, learners[0].batch); return RL_E_INVALID; }
         if (!r.state || !r.state_prime || !r.action || !r.reward || !r.done || !r.count || (draw && !r.age) || r.capacity < 1 || r.capacity > 0x7fffffff) {
             rl_set_error("%s: replay %d incomplete (state / state_prime / action / reward / done / %scount, capacity in [1, 2^31))", who, i, draw ? "age / " : ""); return RL_E_INVALID;
         }
@@ -888,6 +899,50 @@ int rl_learn_td(rl_world* h, const rl_learner* learners, const rl_replay* rings,
     if (int rc = check_td("rl_learn_td", false, h, learners, rings, tds, n_learners, n_steps, slots)) return rc;
     DeviceGuard guard(device_of_pointer(learners[0].params));
     return rl_learn_td_launch(h, learners, rings, tds, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+int rl_learn_td_wide_supported(int kind) { return rl_learn_td_wide_supported_impl(kind); }
+
+size_t rl_learn_td_wide_work_bytes(int kind, int batch)
+{
+    if (!rl_learn_td_wide_supported_impl(kind)) { rl_set_error("rl_learn_td_wide_work_bytes: brain kind %d; rl_learn_td_wide trains RL_PERDQN (4) only (rl_learn_td_wide_supported)", kind); return 0; }
+    if (batch < 1 || batch > RL_LEARN_TD_WIDE_MAX) { rl_set_error("rl_learn_td_wide_work_bytes: batch must be in [1,%d] (got %d)", RL_LEARN_TD_WIDE_MAX, batch); return 0; }
+    return rl_learn_td_wide_work_bytes_impl(batch);
+}
+
+int rl_learn_td_wide_draw(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
+                          int32_t* slots, void* stream)
+{
+    if (int rc = check_td("rl_learn_td_wide_draw", true, h, learners, rings, tds, n_learners, n_steps, slots, RL_LEARN_TD_WIDE_MAX, true,
+                          "rl_learn_td_wide_supported", "rl_learn_td_wide_draw")) return rc;
+    DeviceGuard guard(device_of_pointer(slots));
+    return rl_learn_td_wide_draw_launch(h, learners, rings, tds, n_learners, n_steps, slots, (hipStream_t)stream);
+}
+
+int rl_learn_td_wide_draw_rank(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
+                               int stratified, int32_t* const* order, double* const* cum, void* const* work, int32_t* slots, void* stream)
+{
+    const char* who = "rl_learn_td_wide_draw_rank";
+    if (h && !order) { rl_set_error("%s: null order", who); return RL_E_INVALID; }
+    if (h && !cum) { rl_set_error("%s: null cum", who); return RL_E_INVALID; }
+    if (h && !work) { rl_set_error("%s: null work", who); return RL_E_INVALID; }
+    if (int rc = check_td(who, true, h, learners, rings, tds, n_learners, n_steps, slots, RL_LEARN_TD_WIDE_MAX, true,
+                          "rl_learn_td_wide_supported", who)) return rc;
+    if (int rc = check_draw_rank_buffers(who, learners, n_learners, n_steps, order, cum, work)) return rc;
+    DeviceGuard guard(device_of_pointer(slots));
+    return rl_learn_td_wide_draw_rank_launch(h, learners, rings, tds, n_learners, n_steps, stratified, order, cum, work, slots, (hipStream_t)stream);
+}
+
+int rl_learn_td_wide(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
+                     const int32_t* slots, void* const* work, void* stream)
+{
+    if (h && !work) { rl_set_error("rl_learn_td_wide: null work"); return RL_E_INVALID; }
+    if (int rc = check_td("rl_learn_td_wide", false, h, learners, rings, tds, n_learners, n_steps, slots, RL_LEARN_TD_WIDE_MAX, true,
+                          "rl_learn_td_wide_supported", "rl_learn_td_wide_draw")) return rc;
+    for (int i = 0; i < n_learners; ++i)
+        if (!work[i]) { rl_set_error("rl_learn_td_wide: work[%d] must not be null (rl_learn_td_wide_work_bytes)", i); return RL_E_INVALID; }
+    DeviceGuard guard(device_of_pointer(learners[0].params));
+    return rl_learn_td_wide_launch(h, learners, rings, tds, n_learners, n_steps, slots, work, (hipStream_t)stream);
 }
 
 // rl_learn_td_stamp reads neither batch, min_size, keys, beta nor p_new: its own check, argument by argument

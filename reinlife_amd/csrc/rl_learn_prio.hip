@@ -179,3 +179,11 @@ int rl_learn_td_draw_launch(rl_world* h, const rl_learner* learners, const rl_re
 {
     return prio_draw_launch<true>("rl_learn_td_draw", h, learners, rings, nullptr, tds, n_learners, n_steps, slots, stream);
 }
+
+// rl_learn_td_wide_draw: the same two launches for batches up to RL_LEARN_TD_WIDE_MAX (one workgroup per draw d = s * batch + j, salted
+// by d) -- at batch <= 64 rl_learn_td_draw's table, bit for bit.
+int rl_learn_td_wide_draw_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners,
+                                 int n_steps, int32_t* slots, hipStream_t stream)
+{
+    return prio_draw_launch<true>("rl_learn_td_wide_draw", h, learners, rings, nullptr, tds, n_learners, n_steps, slots, stream);
+}

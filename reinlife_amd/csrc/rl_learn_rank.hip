@@ -460,3 +460,12 @@ int rl_learn_td_draw_rank_launch(rl_world* h, const rl_learner* learners, const 
 {
     return prank_launch("rl_learn_td_draw_rank", h, learners, rings, nullptr, tds, n_learners, n_steps, stratified, order, cum, work, slots, stream);
 }
+
+// rl_learn_td_wide_draw_rank: the same eight launches for batches up to RL_LEARN_TD_WIDE_MAX (one thread per draw d = s * batch + j, salted
+// by d; stratified cuts the total into `batch` segments) -- at batch <= 64 rl_learn_td_draw_rank's table, bit for bit.
+int rl_learn_td_wide_draw_rank_launch(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners,
+                                      int n_steps, int stratified, int32_t* const* order, double* const* cum, void* const* work, int32_t* slots,
+                                      hipStream_t stream)
+{
+    return prank_launch("rl_learn_td_wide_draw_rank", h, learners, rings, nullptr, tds, n_learners, n_steps, stratified, order, cum, work, slots, stream);
+}

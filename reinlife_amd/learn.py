@@ -1,4 +1,4 @@
-"""DeviceLearner: what a DQN (also on wide minibatches: wide_batch=, rl_learn_wide), D3QN (also on wide minibatches: dueling_batch=, rl_learn_dueling_wide), (prioritized=True) PERD3QN, (rollout=True) PPO (also on wide rollouts: rollout_batch=, rl_learn_ppo_wide) or (td_priority=True) PERDQN brain needs to learn on
+"""DeviceLearner: what a DQN (also on wide minibatches: wide_batch=, rl_learn_wide), D3QN (also on wide minibatches: dueling_batch=, rl_learn_dueling_wide), (prioritized=True) PERD3QN, (rollout=True) PPO (also on wide rollouts: rollout_batch=, rl_learn_ppo_wide) or (td_priority=True) PERDQN (also on wide minibatches: td_batch=, rl_learn_td_wide) brain needs to learn on
 the device (rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo / rl_learn_td, include/reinlife_hip.h) -- the flat f32 master parameters,
 the target network, Adam's moments, the step / call counters and the packed weights the acting kernels read, all as device tensors.
 
@@ -47,7 +47,11 @@ the reference makes it); the loss is mean(is_weight) * mean((pred - target)^2), 
 (p_i / min_j p_j) ** -beta over the batch.  learn() copies model -> target_model after every trigger, so sync_target is always on.
 Deviations: Memory.sample is stratified through the sum tree -- here every draw is independent with probability p_i / sum p, by content
 key, with replacement (DeviceWorlds.draw_td); the schedule is the caller's (once per `learn_every` episodes), so epsilon decays once per
-update made, not once per agent trigger -- a smaller explore_step restores the reference's rate in wall-clock terms."""
+update made, not once per agent trigger -- a smaller explore_step restores the reference's rate in wall-clock terms.
+DeviceLearner(brain, device, ring, td_priority=True, td_batch=B) is the same learner on wide minibatches of B <= 2048 rows (rl_learn_td_wide,
+this build's own: 64-row tiles side by side, the importance weights' minimum and mean taken over the whole batch by a pass of their own in
+front of every step's tiles, the priorities of all B rows rewritten); it also owns that entry point's work buffer, and its draws are
+rl_learn_td_wide_draw and rl_learn_td_wide_draw_rank."""
 import copy
 import ctypes as C
 from typing import Callable, NamedTuple
@@ -87,6 +91,7 @@ class Entry(NamedTuple):
     draw: str = None                 # its own draw entry (None: the uniform draws, draw_slots / draw_slots_rank)
     launches: Callable = lambda n_steps: 1   # what one call of n_steps counts as
     per_epoch: bool = False          # launches takes (n_steps, k_epoch): the count depends on the largest k_epoch among the call's learners
+    draw_rank: str = None            # its own prefix-sum draw entry (None: the family's, as DeviceWorlds.draw_*_rank names it)
 
     supported = property(lambda e: e.name + "_supported")
     work_bytes = property(lambda e: e.name + "_work_bytes" if e.narrow else None)
@@ -116,9 +121,17 @@ ENTRIES = (
 # ENTRIES stays these eight rows: tests count them (tests/test_learn_td_stamp_cpu.py, tests/test_learn_prio_draw_rank_cpu.py).  The rows added
 # since stand in MORE_ENTRIES, and the layer reads ALL_ENTRIES = ENTRIES + MORE_ENTRIES: what is said above of a row's index and of the order
 # the keyword rows are tried in holds for that table, and a new row goes to the END of MORE_ENTRIES.
+# The one exception to "the END": rl_learn_td_wide stands IN FRONT of rl_learn_ppo_wide, because tests/test_learn_ppo_wide_cpu.py pins
+# ALL_ENTRIES[-1] to that row.  The index is compared between the ranks of ONE run (Environment._align_learners), never stored, so
+# rl_learn_ppo_wide's moving from 8 to 9 changes no run; rollout_batch names td_batch as a conflict, since it is now tried first.
 MORE_ENTRIES = (
+    Entry("rl_learn_td_wide", "PERDQN", "td", ring_rows="memory_size", keyword="td_batch", needs="td_priority",
+          conflicts=("wide_batch", "dueling_batch", "prioritized", "prioritized_batch", "rollout", "rollout_batch"), narrow="rl_learn_td",
+          batch_max="LEARN_TD_WIDE_MAX", one_batch=True, side=_lib.TdPrio, side_tensors=("priority", "keys", "seen", "beta_is"),
+          draw="rl_learn_td_wide_draw", draw_rank="rl_learn_td_wide_draw_rank",
+          launches=lambda n_steps: 3 * n_steps + 3),   # check, the weights pass, the tiles and the update per step, target / counters / beta, pack
     Entry("rl_learn_ppo_wide", "PPO", "ppo", has_target=False, keyword="rollout_batch", needs="rollout",
-          conflicts=("wide_batch", "dueling_batch", "prioritized", "prioritized_batch", "td_priority"), narrow="rl_learn_ppo",
+          conflicts=("wide_batch", "dueling_batch", "prioritized", "prioritized_batch", "td_priority", "td_batch"), narrow="rl_learn_ppo",
           batch_max="LEARN_PPO_WIDE_MAX", one_batch=True, side=_lib.Ppo, side_tensors=("keys", "seen", "fresh"), draw="rl_learn_rollout_wide",
           launches=lambda n_steps, k_epoch: 3 * n_steps * k_epoch + 3, per_epoch=True),   # check, the two tile passes and the update per rollout and epoch, counters, pack
 )
@@ -140,12 +153,12 @@ def _spelled(keyword):
 
 class DeviceLearner:
     def __init__(self, brain, device="cuda:0", ring=None, prioritized=False, rollout=False, td_priority=False, prioritized_batch=None, *,
-                 rollout_batch=None, wide_batch=None, dueling_batch=None):
-        # (the keywords behind `*` are keyword-only: rollout_batch stands in front of wide_batch and dueling_batch, whose place as the
-        # signature's last two names is pinned, and a caller that passed those two by position must get a TypeError, not another keyword)
+                 td_batch=None, rollout_batch=None, wide_batch=None, dueling_batch=None):
+        # (the keywords behind `*` are keyword-only: td_batch and rollout_batch stand in front of wide_batch and dueling_batch, whose place
+        # as the signature's last two names is pinned, and a caller that passed those two by position must get a TypeError, not another keyword)
         lib = _lib.lib()
         given = dict(prioritized=prioritized, rollout=rollout, td_priority=td_priority, prioritized_batch=prioritized_batch, wide_batch=wide_batch,
-                     dueling_batch=dueling_batch, rollout_batch=rollout_batch)
+                     dueling_batch=dueling_batch, rollout_batch=rollout_batch, td_batch=td_batch)
         given = {k: v for k, v in given.items() if (v is not None if k.endswith("_batch") else v)}
         # every keyword is an explicit opt-in: entry_of() and ENTRY_BY_METHOD keep answering what they answered
         spec = next((e for e in reversed(ALL_ENTRIES) if e.keyword in given), None)

@@ -512,7 +512,10 @@ class DeviceWorlds:
         the reference's Memory on the device (rl_learn_td_draw) -- first every row appended since the last draw gets the one priority
         append_sample gives (learner.p_new), then each draw takes a row with probability priority / sum, with replacement, by a key of the
         rows' content: the same rows whatever slots they sit in (the reference's sample() is stratified through its sum tree; here the
-        draws are independent).  Device int32 [len(learners), n_steps, batch], queued on the current stream."""
+        draws are independent).  Device int32 [len(learners), n_steps, batch], queued on the current stream.
+        A list of wide PERDQN learners (DeviceLearner(..., td_priority=True, td_batch=B)) goes to rl_learn_td_wide_draw: the same two
+        launches and the same arithmetic for batches up to 2048 (B <= 64: rl_learn_td_draw's table).  The learners of a call are all of
+        the one kind or all of the other."""
         return self._draw_side("draw_td", learners, n_steps, _lib.TdPrio, "a PERDQN one (DeviceLearner(..., td_priority=True))")
 
     def draw_prioritized_rank(self, learners, n_steps, stratified=False):
@@ -532,8 +535,15 @@ class DeviceWorlds:
         """draw_td() by that sampler (rl_learn_td_draw_rank): fresh rows get learner.p_new, a row's weight is its stored priority.
         stratified=True (the default) is the reference's Memory.sample(): the total is cut into `batch` segments and draw j takes one
         uniform in segment j -- over the rows in content-key order, so the same rows whatever slots they sit in.  Device int32
-        [len(learners), n_steps, batch], queued on the current stream."""
-        return self._draw_side_rank("draw_td_rank", "rl_learn_td_draw_rank", learners, n_steps, stratified, _lib.TdPrio,
+        [len(learners), n_steps, batch], queued on the current stream.
+        A list of wide PERDQN learners (DeviceLearner(..., td_priority=True, td_batch=B)) goes to rl_learn_td_wide_draw_rank (Entry.draw_rank):
+        the same eight launches for batches up to 2048, stratified at B (B <= 64: rl_learn_td_draw_rank's table).  The learners of a call
+        are all of the one kind or all of the other."""
+        entries = {l.entry for l in learners}
+        if len(entries) > 1:
+            raise ValueError("draw_td_rank(): the learners of a call must be of one kind (one entry point), got %s" % sorted(entries))
+        draw = (learners[0].spec.draw_rank if learners else None) or "rl_learn_td_draw_rank"
+        return self._draw_side_rank("draw_td_rank", draw, learners, n_steps, stratified, _lib.TdPrio,
                                     "a PERDQN one (DeviceLearner(..., td_priority=True))")
 
     def stamp_td(self, learners):
@@ -626,7 +636,10 @@ class DeviceWorlds:
         + 3 launches; one batch per call; `slots` must come from draw_prioritized()), a list of wide PPO learners (DeviceLearner(...,
         rollout=True, rollout_batch=B)) to rl_learn_ppo_wide (PPO.learn() on rollouts of B <= 2048 rows, 32-row tiles side by side with one
         GAE recursion over the whole rollout, 3 n_steps k_epoch + 3 launches with the largest k_epoch of the call; one batch per call;
-        `slots` from draw_rollout(), or the caller's own rows with gate=False).  The
+        `slots` from draw_rollout(), or the caller's own rows with gate=False), a list of wide PERDQN learners (DeviceLearner(...,
+        td_priority=True, td_batch=B)) to rl_learn_td_wide (train_model() on minibatches of B <= 2048 rows, 64-row tiles side by side, the
+        importance weights' minimum and mean over the whole batch from a pass in front of every step's tiles, 3 n_steps + 3 launches; one
+        batch per call; `slots` must come from draw_td() / draw_td_rank()).  The
         learners of one call must all belong to one entry point: ValueError otherwise."""
         if not learners:
             return
