@@ -168,7 +168,10 @@ __device__ inline void split8(const float (&x)[8], float sc, f32x4& hi, f32x4& l
 // Weight prefetch ring of one layer for one wave: D K-chunks of A fragments (2 planes each) in flight.  start() only
 // needs the packed pointer, so it is issued BEFORE the wait that precedes the layer (observation staging, the LDS
 // exchange of the previous layer, the head): the first L2 round trip of every layer overlaps that wait.
-template <int TOUT, int NT, int TSTRIDE, int D>
+// REV: the fragments of a step are REQUESTED in reverse ([NT - 1][lo] first, [0][hi] last).  A step's first MFMA reads [0][hi]: loads return in
+// order, so the one s_waitcnt vmcnt in front of it covers the step's other fragments too, where the forward order has the compiler wait
+// again in front of the first use of each later fragment (k_run's certified one-wave tile).
+template <int TOUT, int NT, int TSTRIDE, int D, bool REV = false>
 struct WRing {
     f32x4 a[D][NT][kPlanes];
     gf32x4* p;
@@ -182,9 +185,12 @@ struct WRing {
 #pragma unroll
         for (int d = 0; d < D; ++d)
 #pragma unroll
-            for (int t = 0; t < NT; ++t)
+            for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
-                for (int pl = 0; pl < kPlanes; ++pl) a[d][t][pl] = p[((d * TOUT + t * TSTRIDE) * kPlanes + pl) * 64];
+                for (int pp = 0; pp < kPlanes; ++pp) {
+                    const int t = REV ? NT - 1 - tt : tt, pl = REV ? kPlanes - 1 - pp : pp;
+                    a[d][t][pl] = p[((d * TOUT + t * TSTRIDE) * kPlanes + pl) * 64];
+                }
     }
     // take chunk s out of the ring and refill its slot with chunk s + D (of NS)
     template <int NS>
@@ -201,9 +207,12 @@ struct WRing {
         asm volatile("" : "+v"(p));
         if (s + D < NS) {
 #pragma unroll
-            for (int t = 0; t < NT; ++t)
+            for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
-                for (int pl = 0; pl < kPlanes; ++pl) a[cur][t][pl] = p[(((D - 1) * TOUT + t * TSTRIDE) * kPlanes + pl) * 64];
+                for (int pp = 0; pp < kPlanes; ++pp) {
+                    const int t = REV ? NT - 1 - tt : tt, pl = REV ? kPlanes - 1 - pp : pp;
+                    a[cur][t][pl] = p[(((D - 1) * TOUT + t * TSTRIDE) * kPlanes + pl) * 64];
+                }
         }
     }
 };
@@ -584,7 +593,8 @@ constexpr int kTileConstFloats = 3 * 256 + 2 * 16;
 constexpr int kTileCertFloats = 4;
 
 // Weight ring over the 2 * NS steps of a layer taken as two passes: step i = K-chunk i % NS of output tiles 2 * (i / NS), +1.
-template <int NS, int D, int STEPS = 2 * NS, int TOUT = 4>   // STEPS = NS: one pass only (the caller offsets the base by its tile pair); TOUT: output tiles of the layer
+// REV: request order of a step's four fragments [1][lo], [0][lo], [1][hi], [0][hi] -- the one the step's first MFMA reads comes last (see WRing).
+template <int NS, int D, int STEPS = 2 * NS, int TOUT = 4, bool REV = false>   // STEPS = NS: one pass only (the caller offsets the base by its tile pair); TOUT: output tiles of the layer
 struct WRingH {
     f32x4 a[D][2][kPlanes];
     gf32x4* p;   // tile-pair fragment block of the step the next refill asks for
@@ -600,9 +610,10 @@ struct WRingH {
 #pragma unroll
         for (int d = 0; d < D; ++d)
 #pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int pl = 0; pl < kPlanes; ++pl) a[d][t][pl] = p[off(d) + (t * kPlanes + pl) * 64];
+            for (int j = 0; j < 2 * kPlanes; ++j) {
+                const int t = REV ? 1 - (j & 1) : j / kPlanes, pl = REV ? kPlanes - 1 - j / 2 : j % kPlanes;
+                a[d][t][pl] = p[off(d) + (t * kPlanes + pl) * 64];
+            }
         p += off(D);
         asm volatile("" : "+v"(p));
     }
@@ -615,9 +626,10 @@ struct WRingH {
             for (int pl = 0; pl < kPlanes; ++pl) ac[t][pl] = a[cur][t][pl];
         if (i + D < STEPS) {
 #pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int pl = 0; pl < kPlanes; ++pl) a[cur][t][pl] = p[(t * kPlanes + pl) * 64];
+            for (int j = 0; j < 2 * kPlanes; ++j) {
+                const int t = REV ? 1 - (j & 1) : j / kPlanes, pl = REV ? kPlanes - 1 - j / 2 : j % kPlanes;
+                a[cur][t][pl] = p[(t * kPlanes + pl) * 64];
+            }
             if (i + D + 1 < STEPS) { p += off(i + D + 1) - off(i + D); asm volatile("" : "+v"(p)); }
         }
     }
@@ -642,11 +654,47 @@ __device__ inline void split_lo(float x0, float x1, float sc, float hi, float& l
 #endif
     lo = __builtin_bit_cast(float, l);
 }
-// Slice k of NSLOT of the split of one 8-element B chunk (the same instructions as split8, in the same order): the eight
-// half-pairs hi0 lo0 hi1 lo1 hi2 lo2 hi3 lo3 are dealt to the slots in order.  raw(e) = element e of the chunk.
-template <int NSLOT, typename Raw>
+// Stage ST = 0 .. 3 of one pair's split: the four instructions of split_hi + split_lo, one at a time (same instructions, same operands).
+template <int ST>
+__device__ inline void split_stage(float x0, float x1, float sc, float& hi, float& lo)
+{
+    unsigned h = __builtin_bit_cast(unsigned, hi), l = __builtin_bit_cast(unsigned, lo);
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (ST == 0) asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(x0), "v"(sc));
+    if constexpr (ST == 1) asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(x1), "v"(sc));
+    if constexpr (ST == 2) asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(l) : "v"(x0), "v"(sc), "v"(h));
+    if constexpr (ST == 3) asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(x1), "v"(sc), "v"(h));
+#endif
+    if constexpr (ST < 2) hi = __builtin_bit_cast(float, h);
+    else lo = __builtin_bit_cast(float, l);
+}
+// Slice k of NSLOT of the split of one 8-element B chunk (the same instructions as split8): the eight half-pairs hi0 lo0 hi1 lo1 hi2 lo2
+// hi3 lo3 are dealt to the slots in order.  raw(e) = element e of the chunk.
+// STAGED (k_run's certified one-wave tile): the sixteen instructions are dealt STAGE BY STAGE instead -- mixlo h of pairs
+// 0 .. 3, then their mixhi h, mixlo l, mixhi l -- 16 / NSLOT per slot.  Pair by pair every instruction follows the one whose half-written
+// register it reads, and the compiler pads each such pair with an s_nop (twelve per chunk): its hazard recognizer takes every asm
+// statement for a writer with a destination-select hazard and does not count asm statements as wait states, so a reader is padded
+// unless an instruction the compiler KNOWS (an MFMA, a load, an address add) lies between it and its writer.  Stage by stage, two or
+// three to a slot of k_pass, every reader has an MFMA between itself and its writer (the head's three slots per chunk cannot: four
+// stages, so one s_nop per slot remains there).  Same instructions on the same operands: the halves are the same bits.
+template <int NSLOT, bool STAGED = false, typename Raw>
 __device__ inline void split_slice(int k, Raw&& raw, float sc, f32x4& hi, f32x4& lo)
 {
+    if constexpr (STAGED) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            if (i < (k * 16) / NSLOT || i >= ((k + 1) * 16) / NSLOT) continue;
+            const int q = i & 3;
+            float h = hi[q], l = lo[q];
+            switch (i >> 2) {
+            case 0: split_stage<0>(raw(2 * q), raw(2 * q + 1), sc, h, l); hi[q] = h; break;
+            case 1: split_stage<1>(raw(2 * q), raw(2 * q + 1), sc, h, l); hi[q] = h; break;
+            case 2: split_stage<2>(raw(2 * q), raw(2 * q + 1), sc, h, l); lo[q] = l; break;
+            default: split_stage<3>(raw(2 * q), raw(2 * q + 1), sc, h, l); lo[q] = l; break;
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         if (j < (k * 8) / NSLOT || j >= ((k + 1) * 8) / NSLOT) continue;
@@ -720,6 +768,11 @@ __device__ __forceinline__ void in_split_slot(Raw&& raw, float sc, f32x4& hi, f3
     }
 }
 
+// A REV ring (k_run's certified one-wave tile) also pins every MFMA IN FRONT of its slot: left to itself the scheduler hoists a slot's
+// instructions over their MFMA, and a step's sixteen split instructions then sit in four gaps (2 6 0 2 3 3), not six -- with one s_nop
+// where two stages meet without an MFMA between them, and six instructions against one MFMA's shadow.
+template <typename Ring> struct ring_is_rev { static constexpr bool value = false; };
+template <int NS, int D, int STEPS, int TOUT> struct ring_is_rev<WRingH<NS, D, STEPS, TOUT, true>> { static constexpr bool value = true; };
 // One pass of a layer: K loop over NS chunks for output tiles 2 * HALF, +1.  shadow(slot), slot = 0 .. 6 * NS - 1, follows MFMA `slot`.
 template <int NS, int HALF, typename Ring, typename Shadow>   // Ring: take(step, fragments) -- WRingH (registers) or WStageH (LDS stages)
 __device__ inline void k_pass(Ring& w, const f32x4 (&B)[NS][kPlanes], f32x16& a0, f32x16& a1, Shadow&& shadow)
@@ -730,12 +783,12 @@ __device__ inline void k_pass(Ring& w, const f32x4 (&B)[NS][kPlanes], f32x16& a0
     for (int s = 0; s < NS; ++s) {
         f32x4 ac[2][kPlanes];
         w.take(HALF * NS + s, ac);
-        a0 = mfma16(ac[0][0], B[s][1], a0); shadow(6 * s + 0); __builtin_amdgcn_sched_barrier(0);   // hi.lo
-        a1 = mfma16(ac[1][0], B[s][1], a1); shadow(6 * s + 1); __builtin_amdgcn_sched_barrier(0);
-        a0 = mfma16(ac[0][0], B[s][0], a0); shadow(6 * s + 2); __builtin_amdgcn_sched_barrier(0);   // hi.hi
-        a1 = mfma16(ac[1][0], B[s][0], a1); shadow(6 * s + 3); __builtin_amdgcn_sched_barrier(0);
-        a0 = mfma16(ac[0][1], B[s][0], a0); shadow(6 * s + 4); __builtin_amdgcn_sched_barrier(0);   // lo.hi
-        a1 = mfma16(ac[1][1], B[s][0], a1); shadow(6 * s + 5); __builtin_amdgcn_sched_barrier(0);
+        a0 = mfma16(ac[0][0], B[s][1], a0); if constexpr (ring_is_rev<Ring>::value) __builtin_amdgcn_sched_barrier(0); shadow(6 * s + 0); __builtin_amdgcn_sched_barrier(0);   // hi.lo
+        a1 = mfma16(ac[1][0], B[s][1], a1); if constexpr (ring_is_rev<Ring>::value) __builtin_amdgcn_sched_barrier(0); shadow(6 * s + 1); __builtin_amdgcn_sched_barrier(0);
+        a0 = mfma16(ac[0][0], B[s][0], a0); if constexpr (ring_is_rev<Ring>::value) __builtin_amdgcn_sched_barrier(0); shadow(6 * s + 2); __builtin_amdgcn_sched_barrier(0);   // hi.hi
+        a1 = mfma16(ac[1][0], B[s][0], a1); if constexpr (ring_is_rev<Ring>::value) __builtin_amdgcn_sched_barrier(0); shadow(6 * s + 3); __builtin_amdgcn_sched_barrier(0);
+        a0 = mfma16(ac[0][1], B[s][0], a0); if constexpr (ring_is_rev<Ring>::value) __builtin_amdgcn_sched_barrier(0); shadow(6 * s + 4); __builtin_amdgcn_sched_barrier(0);   // lo.hi
+        a1 = mfma16(ac[1][1], B[s][0], a1); if constexpr (ring_is_rev<Ring>::value) __builtin_amdgcn_sched_barrier(0); shadow(6 * s + 5); __builtin_amdgcn_sched_barrier(0);
     }
 }
 
@@ -748,12 +801,21 @@ __device__ inline void max3_abs(float& m, float a, float b)   // m = max(m, |a|,
 
 // Epilogue of two finished output tiles, one accumulator register per step (32 steps): y = relu(acc * (unscale * row_un) + bias),
 // m = max(m, y).  The constants of quarter Q (4 registers) are read from LDS while quarter Q - 1 is worked on.
-struct EpiStream {
+// REV: a quarter's biases are requested BEFORE its unscales.  A step multiplies by the unscale first: LDS reads return in order, so the one
+// s_waitcnt lgkmcnt in front of that product covers the bias too, where the forward order has the compiler wait once for each (k_run's
+// certified one-wave tile).
+template <bool REV>
+struct EpiStreamT {
     const float* c;   // LDS: the layer's 256 constants + 32 * half  ([tile][half][unscale 16 | bias 16])
     f32x4 un[2], bi[2];
     __device__ inline void fetch(int t, int Q)   // quarter Q = 0 .. 7 of the tile pair (t = first tile of the pair)
     {
         const float* q = c + (t + (Q >> 2)) * 64 + 4 * (Q & 3);
+        if constexpr (REV) {
+            bi[Q & 1] = *(const f32x4*)(q + 16);
+            un[Q & 1] = *(const f32x4*)q;
+            return;
+        }
         un[Q & 1] = *(const f32x4*)q;
         bi[Q & 1] = *(const f32x4*)(q + 16);
     }
@@ -767,30 +829,31 @@ struct EpiStream {
         m = fmaxf(m, y);
     }
 };
+using EpiStream = EpiStreamT<false>;
 
 // head (8 / 1 outputs padded to one A tile) over K = 128, its input split chunk by chunk ahead of the MFMAs that use it.
 // raw(c, e): element e of B chunk c (= register 8 * (c & 1) + e of activation tile c >> 1).
-template <int D, int NCH = 8, typename Raw>   // NCH: K-chunks of the head's input this wave holds (8 = 128 features)
-__device__ inline void head_stream(WRing<1, 1, 1, D>& w, const f32x4& un4, Raw&& raw, float sc, float row_un, float (&out)[4])
+template <int D, int NCH = 8, bool STAGED = false, typename Raw>   // NCH: K-chunks of the head's input this wave holds (8 = 128 features); STAGED: split_slice's, with a REV ring
+__device__ inline void head_stream(WRing<1, 1, 1, D, STAGED>& w, const f32x4& un4, Raw&& raw, float sc, float row_un, float (&out)[4])
 {
     f32x16 a0, a1, a2;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { a0[r] = 0.0f; a1[r] = 0.0f; a2[r] = 0.0f; }
     f32x4 B[NCH][kPlanes];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) split_slice<3>(k, [&](int e) { return raw(0, e); }, sc, B[0][0], B[0][1]);
+    for (int k = 0; k < 3; ++k) split_slice<3, STAGED>(k, [&](int e) { return raw(0, e); }, sc, B[0][0], B[0][1]);
 #pragma unroll
     for (int s = 0; s < NCH; ++s) {
         f32x4 ac[1][kPlanes];
         w.template next<NCH>(s, ac);
         a0 = mfma16(ac[0][0], B[s][1], a0);
-        if (s + 1 < NCH) split_slice<3>(0, [&](int e) { return raw(s + 1, e); }, sc, B[(s + 1) % NCH][0], B[(s + 1) % NCH][1]);
+        if (s + 1 < NCH) split_slice<3, STAGED>(0, [&](int e) { return raw(s + 1, e); }, sc, B[(s + 1) % NCH][0], B[(s + 1) % NCH][1]);
         __builtin_amdgcn_sched_barrier(0);
         a1 = mfma16(ac[0][0], B[s][0], a1);
-        if (s + 1 < NCH) split_slice<3>(1, [&](int e) { return raw(s + 1, e); }, sc, B[(s + 1) % NCH][0], B[(s + 1) % NCH][1]);
+        if (s + 1 < NCH) split_slice<3, STAGED>(1, [&](int e) { return raw(s + 1, e); }, sc, B[(s + 1) % NCH][0], B[(s + 1) % NCH][1]);
         __builtin_amdgcn_sched_barrier(0);
         a2 = mfma16(ac[0][1], B[s][0], a2);
-        if (s + 1 < NCH) split_slice<3>(2, [&](int e) { return raw(s + 1, e); }, sc, B[(s + 1) % NCH][0], B[(s + 1) % NCH][1]);
+        if (s + 1 < NCH) split_slice<3, STAGED>(2, [&](int e) { return raw(s + 1, e); }, sc, B[(s + 1) % NCH][0], B[(s + 1) % NCH][1]);
         __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
@@ -1008,7 +1071,7 @@ __device__ inline bool policy_tile1s(const IO& io, int lane, int role = 0, const
     const float* const consts = (const float*)(rl_dyn_lds + io.c_lds_off) + 32 * h;   // + 256 per layer: l1, l2a, l2b
     const float* const hconsts = (const float*)(rl_dyn_lds + io.c_lds_off) + 768;     // heads: [un 8 | bias 8] advantage, value
     RL_PMARK1(1);
-    WRingH<kInChunks, D, PAIR ? kInChunks : 2 * kInChunks> w1;
+    WRingH<kInChunks, D, PAIR ? kInChunks : 2 * kInChunks, 4, kRef> w1;
     w1.start(packed + L.l1 + (PAIR ? role * (2 * kPlanes * 64 * 4) : 0), lane);
     // ---- the lane's half of its observation row, chunk by chunk: x[row][16c + 8h + 0..7] (see policy_tile1)
     f32x4 X[kInChunks][2];
@@ -1118,7 +1181,7 @@ __device__ inline bool policy_tile1s(const IO& io, int lane, int role = 0, const
     auto xraw = [&](int c, int e) { return X[c][e >> 2][e & 3]; };
     // ---- input layer
     f32x16 F[4];
-    EpiStream ep;
+    EpiStreamT<kRef> ep;
     if constexpr (XM >= 1) {
         auto x0 = [&](int e) { return xraw(0, e); };
         in_split_slot<XM, 0, 0>(x0, sc0, B1[0][0], B1[0][1]); in_split_slot<XM, 0, 1>(x0, sc0, B1[0][0], B1[0][1]);
@@ -1130,16 +1193,16 @@ __device__ inline bool policy_tile1s(const IO& io, int lane, int role = 0, const
         });
     } else {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) split_slice<6>(k, [&](int e) { return xraw(0, e); }, sc0, B1[0][0], B1[0][1]);
+        for (int k = 0; k < 6; ++k) split_slice<6, kRef>(k, [&](int e) { return xraw(0, e); }, sc0, B1[0][0], B1[0][1]);
         RL_PMARK1(2);
         k_pass<kInChunks, 0>(w1, B1, F[0], F[1], [&](int slot) {
             const int c = slot / 6 + 1;
-            if (c < kInChunks) split_slice<6>(slot % 6, [&](int e) { return xraw(c, e); }, sc0, B1[c][0], B1[c][1]);
+            if (c < kInChunks) split_slice<6, kRef>(slot % 6, [&](int e) { return xraw(c, e); }, sc0, B1[c][0], B1[c][1]);
         });
     }
     float mrow = 0.0f;
     const int64_t l2 = (PAIR && role) ? L.l2b : L.l2a, hd = (PAIR && role) ? L.hb : L.ha;
-    WRingH<8, D> w2;
+    WRingH<8, D, 16, 4, kRef> w2;
     f32x4 B2[8][kPlanes];
     float sc1, un1;
     auto fraw = [&](int c, int e) { return F[c >> 1][8 * (c & 1) + e]; };
@@ -1195,14 +1258,14 @@ __device__ inline bool policy_tile1s(const IO& io, int lane, int role = 0, const
         row_scale(mrow, sc1, un1);
         // relu(feature) feeds both branches (PERD3QN.py:200-201): B2 chunk 2t + c = registers 8c .. 8c+7 of tile t
 #pragma unroll
-        for (int k = 0; k < 6; ++k) split_slice<6>(k, [&](int e) { return fraw(0, e); }, sc1, B2[0][0], B2[0][1]);
+        for (int k = 0; k < 6; ++k) split_slice<6, kRef>(k, [&](int e) { return fraw(0, e); }, sc1, B2[0][0], B2[0][1]);
     }
     RL_PMARK1(4);
     // ---- advantage branch
     f32x16 A[4];
     k_pass<8, 0>(w2, B2, A[0], A[1], [&](int slot) {
         const int c = slot / 6 + 1;
-        if (!PAIR && c < 8) split_slice<6>(slot % 6, [&](int e) { return fraw(c, e); }, sc1, B2[c][0], B2[c][1]);
+        if (!PAIR && c < 8) split_slice<6, kRef>(slot % 6, [&](int e) { return fraw(c, e); }, sc1, B2[c][0], B2[c][1]);
     });
     mrow = 0.0f;
     ep.c = consts + ((PAIR && role) ? 512 : 256);
@@ -1211,7 +1274,7 @@ __device__ inline bool policy_tile1s(const IO& io, int lane, int role = 0, const
         if (slot >= 2 && slot < 34) ep.step(0, slot - 2, A[0], A[1], un1, mrow);
     });
     RL_PMARK1(5);
-    WRing<1, 1, 1, D> wh;
+    WRing<1, 1, 1, D, kRef> wh;
     [[maybe_unused]] int lane_h = 0;   // TileRef: the head's lane index
     if constexpr (kRef) { lane_h = tile_lane_fresh(); wh.start(packed + hd, lane_h, 0); }
     else wh.start(packed + hd, lane, 0);
@@ -1244,7 +1307,7 @@ __device__ inline bool policy_tile1s(const IO& io, int lane, int role = 0, const
         return false;
     }
     if constexpr (kRef) {   // the action without V -- or nothing stored and `true`: the caller runs the full tile
-        head_stream<D>(wh, *(const f32x4*)(hconsts + 4 * (lane_h >> 5)), araw, sc2, un2, adv);
+        head_stream<D, 8, true>(wh, *(const f32x4*)(hconsts + 4 * (lane_h >> 5)), araw, sc2, un2, adv);
         const float* const kc = hconsts + kTileConstFloats - 768;
         bool failed = false;
         tile1_finish_cert<KIND>(io, lane, adv, draw, hconsts, __builtin_fmaf(kc[1], zrow, kc[0]), [&]() { failed = true; });

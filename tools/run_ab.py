@@ -1,11 +1,13 @@
 """A/B of two builds of the library on the same box: rl_run per-tick time at 256 worlds, alternating, N rounds (tuning; GPU).
-   python tools/run_ab.py libA.so libB.so [rounds]"""
+   python tools/run_ab.py libA.so libB.so [rounds]      RL_AB_WORKLOAD=c5, RL_AB_TRAIN=1, RL_AB_STATIC=0: another kernel instantiation"""
 import os, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 code = r'''
 import os, sys, time
 sys.path.insert(0, %r)
 import torch, bench
+if os.environ.get("RL_AB_STATIC") == "0":   # the FIXED = false instantiations: the same workload with static_families=False
+    bench.WORKLOADS[os.environ.get("RL_AB_WORKLOAD", "c4")]["static_families"] = False
 args = __import__("argparse").Namespace(worlds=256, workload=os.environ.get("RL_AB_WORKLOAD", "c4"), seed=1)
 a = bench.make_worlds(args, 0, "cuda:0")
 kw = {}
