@@ -44,6 +44,16 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     WITH replacement, where the reference's random.sample (DQN.py:100) draws without -- and by a key of the rows' content mixed with
     Philox bits rather than by slot, because the worlds append to a ring in a timing-dependent order: a second identical call gives the
     same parameters bit for bit unless one chunk appends more than a ring holds.
+    learn="reference": the call a ReinLife user already has -- trainer([DQN(), DQN()]) -- trains, and from the same seeds it trains the
+    way the reference does.  One world, rng="reference", static_families=True, training=True, per_agent_api=False, fused None or False,
+    a single rank, and none of the learn_* keywords below (ValueError otherwise, before a device is touched): the brains' own attributes
+    set the hyperparameters.  The loop is act -> step -> env.learn_reference(n_epi) -> update_env: one capture of the tick's transitions,
+    then, per agent of the post-step list with age > 1, in list order, what its brain's learn() does when `age % train_freq == 0 or dead`
+    -- DQN: five minibatches of random.sample(deque, 32) once the deque holds more than 1000 rows, target copy (rl_learn, one launch);
+    D3QN: once n_epi > exploration one update on random.sample(deque, batch_size), eval -> target when n_epi is a multiple of
+    soft_update_freq (rl_learn_dueling); PPO: one learn() over all rows stored since the last one, k_epoch epochs (rl_learn_ppo up to 32
+    rows, rl_learn_ppo_wide up to 2048; a longer list is a ValueError).  random.sample consumes the process-global `random` stream as in
+    the reference, so the run's draws stay the reference's.  PERD3QN and PERDQN brains stay frozen in this mode (a warning names them).
     learn_kinds (default None = ("DQN",): exactly the above): the brain methods that train.  learn_kinds=("DQN", "D3QN") also trains every
     D3QN brain, through rl_learn_dueling: its ring holds brain.capacity rows (10,000, D3QN.py:62); after an episode `last` that is a
     multiple of `learn_every` (default: the smallest train_freq of all learners) and greater than brain.exploration (D3QN.py:121) one
@@ -170,6 +180,12 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     if learn == "device" and (per_agent_api or fused is False):
         raise ValueError("trainer(learn='device') needs the fused path (fused=True, per_agent_api=False): the replay rings are filled "
                          "inside the multi-tick launches")
+    if learn == "reference" and per_agent_api:
+        raise ValueError("trainer(learn='reference') needs per_agent_api=False: the brains' own learn() stays a no-op, the tick's learning "
+                         "calls are made by env.learn_reference(n_epi)")
+    if learn == "reference" and fused:
+        raise ValueError("trainer(learn='reference') needs fused=None or fused=False: it is the tick-by-tick loop of one world with "
+                         "rng='reference' (the fused path is learn='device')")
     env = Environment(width=width, height=height, max_agents=max_agents, brains=brains, grid_size=24,
                       static_families=static_families, update_interval=update_interval, print_results=print_results,
                       interactive_results=visualize_results, google_colab=google_colab, training=training,
@@ -204,6 +220,8 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
             else:
                 env.act(n_epi)
                 env.step()
+                if learn == "reference":       # trainer.py:95-96: every agent's learn(), as one capture and the schedule's calls
+                    env.learn_reference(n_epi)
                 env.update_env(n_epi)
             if render:  # trainer.py:101-102
                 env.render(fps=120)

@@ -7,7 +7,8 @@ The per-agent learn() of the reference's brains is accepted and ignored, so that
 running (a warning is issued once).  DQN brains learn on the device instead, through trainer(learn="device") / learn.DeviceLearner
 (rl_learn), D3QN brains with learn_kinds=("DQN", "D3QN") (rl_learn_dueling) and PERD3QN brains with learn_prioritized=True
 (rl_learn_prioritized, with their prioritised memory), PPO brains with learn_rollout=True (rl_learn_ppo) and PERDQN brains with
-learn_td_priority=True (rl_learn_td, with the reference's memory and importance weights).
+learn_td_priority=True (rl_learn_td, with the reference's memory and importance weights).  On one world, trainer(learn="reference") trains
+DQN, D3QN and PPO brains on the reference's own per-agent schedule and draws (learn_reference.py); learn() itself stays a no-op there too.
 """
 import random
 import warnings

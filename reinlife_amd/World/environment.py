@@ -157,6 +157,7 @@ class AgentView:
 class Environment:
     _DRAW_KINDS = ("DQN", "D3QN", "PERD3QN", "PERDQN")   # the keys of learn_draw as a dict: the brain methods whose draw has a rank variant
     _DRAW_FAMILY = {"dqn": "DQN", "dueling": "D3QN", "prioritized": "PERD3QN", "td": "PERDQN"}   # ... per family of learn.FAMILIES
+    log_reference_calls = False   # learn="reference": keep every Call in self.reference_calls (a class attribute: trainer() builds its own environment)
 
     def __init__(self, width=30, height=30, brains=None, grid_size=16, max_agents=50, update_interval=500, print_results=True,
                  static_families=True, interactive_results=False, google_colab=False, training=True, save=False,
@@ -166,8 +167,9 @@ class Environment:
                  learn_td_priority=None, learn_td_stamp=None, learn_ranks=None, learn_batch=None, learn_draw=None):
         if not brains:
             raise ValueError("Environment needs a non-empty list of brains")
-        if learn not in (None, "device"):
-            raise ValueError("learn must be None (the brains stay as they are) or 'device' (DQN brains train through rl_learn), got %r" % (learn,))
+        if learn not in (None, "device", "reference"):
+            raise ValueError("learn must be None (the brains stay as they are), 'device' (DQN brains train through rl_learn) or 'reference' (one world, "
+                             "the reference's own schedule and draws: DQN, D3QN and PPO brains train), got %r" % (learn,))
         # learn_kinds: the brain methods that train under learn="device".  None = ("DQN",): what learn="device" always did; "D3QN" is an
         # explicit opt-in (rl_learn_dueling).  Checked here, before a device is touched.
         if learn_kinds is not None and learn != "device":
@@ -294,6 +296,7 @@ class Environment:
         # learn_steps: minibatch updates per call -- an int is the DQN learners' (as always), a dict by method name sets it per kind;
         # D3QN defaults to 1 (D3QNAgent.train() makes one update), and so does PERDQN (train_model())
         self.learn_steps_of = {"DQN": 5, "D3QN": 1, "PERDQN": 1}
+        steps_given = learn_steps   # (as the caller spelled it: learn="reference" takes none)
         if isinstance(learn_steps, dict):
             bad = [k for k in learn_steps if k not in ENTRY_BY_METHOD and k != "PERDQN"]
             if bad:
@@ -360,6 +363,12 @@ class Environment:
                 raise ValueError("learn='device' captures transitions for at most %d brains (got %d)" % (_lib.MAX_CAPTURE_BRAINS, len(brains)))
             if min(self.learn_steps_of.values()) < 1 or (learn_every is not None and int(learn_every) < 1):
                 raise ValueError("learn_steps and learn_every must be >= 1")
+        self.schedule = None        # learn="reference": the host schedule (learn_reference.ReferenceSchedule)
+        self._ppo_narrow = {}       # ... and per PPO brain the rl_learn_ppo learner over the wide learner's tensors
+        self._learned = False       # ... learn_reference() ran since the last step()
+        self.reference_calls = []   # ... every Call made so far as (n_epi, Call), while log_reference_calls is on (tests, diagnostics)
+        if learn == "reference":    # every condition is checked before a device is touched
+            self._check_reference(brains, n_worlds, static_families, training, learn_every, steps_given)
         self.best_agents = []
         # environment.py:118: the painter is built first (pastel colours draw from `random` here, its background tiles at
         # the first render() -- both matter for same-seed runs)
@@ -429,8 +438,97 @@ class Environment:
                                     + (("PERDQN (TD priorities)",) if self.learn_td_priority else ()), draw=self.learn_draw)
             if self.learn_ranks:
                 self._align_learners()
+        elif learn == "reference":
+            self._build_reference(brains, max_agents)
         elif training:
             warn_inference_only()
+
+    def _check_reference(self, brains, n_worlds, static_families, training, learn_every, learn_steps):
+        """The conditions of learn="reference", each a ValueError that names it.  (The other learn_* keywords have refused a learn that
+        is not 'device' by now, each in its own words.)"""
+        if n_worlds != 1:
+            raise ValueError("learn='reference' needs n_worlds=1: it is the reference's own per-agent schedule for its one world (got n_worlds=%r); "
+                             "learn='device' trains many worlds" % (n_worlds,))
+        if self.world_size > 1:
+            raise ValueError("learn='reference' runs on a single rank (world size %d)" % self.world_size)
+        if self.rng != "reference":
+            raise ValueError("learn='reference' needs rng='reference' (random.sample's draws interleave with the coins of act() and the draws of "
+                             "update_env() on the process-global generators); this environment has rng=%r" % self.rng)
+        if not static_families:
+            raise ValueError("learn='reference' needs static_families=True: per-gene brain copies (non-static families) do not learn yet")
+        if not training:
+            raise ValueError("learn='reference' needs training=True")
+        if learn_every is not None:
+            raise ValueError("learn='reference' takes no learn_every: a brain trains when an agent's age is a multiple of its train_freq or the agent died")
+        if isinstance(learn_steps, dict) or learn_steps != 5:
+            raise ValueError("learn='reference' takes no learn_steps: the brains' own train() sets the updates per call (DQN 5, D3QN 1)")
+        if len(brains) > _lib.MAX_CAPTURE_BRAINS:
+            raise ValueError("learn='reference' captures transitions for at most %d brains (got %d)" % (_lib.MAX_CAPTURE_BRAINS, len(brains)))
+
+    def _build_reference(self, brains, max_agents):
+        """The learners, rings and schedule of learn="reference" (learn_reference.py): a ring of the deque's maxlen + slot_cap rows per
+        learning brain (the floor for the others, whose rows nobody reads), one DeviceLearner per DQN / D3QN / PPO brain whose packed
+        tensor is the brain's acting weights from here on.  A PPO brain's learner is the wide one, built once for PPO_LIST_MAX rows; the
+        narrow entry's learner shares every tensor with it."""
+        from ..learn_reference import PPO_LIST_MAX, BrainSpec, ReferenceSchedule
+        slack = _lib.slot_cap_for(max_agents)
+        self.schedule = ReferenceSchedule([BrainSpec.of(b) for b in brains], slack)
+        specs = self.schedule.specs
+        self.ring_floor = slack
+        self.ring_rows = [self.schedule.ring_rows(k) if specs[k] else slack for k in range(len(brains))]
+        ppo = any(s is not None and s.method == "PPO" for s in specs)
+        self.worlds.enable_capture(self.ring_rows, **({"with_prob": True} if ppo else {}))
+        for k, s in enumerate(specs):
+            if s is None:
+                continue
+            ring = self.worlds.replays[k]
+            if s.method == "PPO":
+                wide = self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=ring, rollout=True, rollout_batch=PPO_LIST_MAX)
+                narrow = self._ppo_narrow[k] = DeviceLearner(brains[k], self.worlds.device, ring=ring, rollout=True)
+                for name in ("params", "adam_m", "adam_v", "state", "packed") + wide.spec.side_tensors:
+                    setattr(narrow, name, getattr(wide, name))
+            else:
+                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=ring)
+        frozen = ["%d (%s)" % (k, b.method) for k, b in enumerate(brains) if k not in self.learners]
+        if frozen:
+            warn_inference_only(frozen, ("DQN", "D3QN", "PPO"), mode="reference")
+        if not self.learners:
+            raise ValueError("learn='reference': none of the brains is of a kind that trains in this mode (DQN, D3QN, PPO)")
+
+    def learn_reference(self, n_epi=0):
+        """trainer.py:95-96 -- Agent.learn() for every agent of the post-step list -- between step() and update_env(n_epi): one
+        capture of the tick's transitions (rl_capture_transitions), then the calls the schedule names, in its order, each one
+        DeviceWorlds.learn with one learner and the slots of the rows random.sample drew (learn_reference.ReferenceSchedule).  The
+        schedule reads the host mirror step() has built; nothing is read back.  Returns the tick's Calls."""
+        if self.learn != "reference":
+            raise ValueError("learn_reference() needs learn='reference' (this environment has learn=%r)" % (self.learn,))
+        if self._phase != "step" or self._learned:
+            raise RuntimeError("learn_reference() belongs between step() and update_env(), once per tick")
+        h = self._host
+        calls = self.schedule.tick(n_epi, zip(h["a_brain"], h["a_age"], h["a_flags"] & _lib.F_DEAD))
+        self._learned = True
+        self.worlds.capture_transitions(with_policy_out=bool(self._ppo_narrow))
+        self.worlds.launches += 1
+        for c in calls:
+            l = self.learners[c.brain]
+            if c.kind == "sync":    # eval -> target without an update: on the same stream, behind the last update
+                l.target.copy_(l.params)
+                self.worlds.launches += 1
+            elif c.kind == "ppo":
+                self._learn_ppo(c.brain, c.slots, c.wide)
+            else:
+                l.sync_target = bool(c.sync_target)
+                self.worlds.learn([l], c.slots.shape[0], slots=c.slots[None])
+        if self.log_reference_calls:
+            self.reference_calls += [(n_epi, c) for c in calls]
+        return calls
+
+    def _learn_ppo(self, brain, slots, wide):
+        """One PPO.learn() on the rows at `slots` ([1][length], storage order) through rl_learn_ppo_wide (wide) or rl_learn_ppo; the
+        batch of the call is the list's length."""
+        l = self.learners[brain] if wide else self._ppo_narrow[brain]
+        l.batch = int(np.asarray(slots).shape[-1])
+        self.worlds.learn([l], 1, slots=np.asarray(slots, np.int32).reshape(1, 1, -1), gate=False)
 
     def _opt_in(self, keyword, value, learn, brains):
         """learn_<keyword>=True, the environment's spelling of DeviceLearner(..., <keyword>=True): None or True, with learn='device' and
@@ -625,6 +723,7 @@ class Environment:
             tape, self._n_empty = self._draw_add_food(nf, npo, ns, ne)
             self.worlds.step_food(self.worlds.make_tape([tape]))
             self._refresh(after="step")
+            self._learned = False
             self._mirrors[0] = self._build_mirror(0, snap)   # (its cell_type predates the food: env.grid fetches its own)
         else:
             self.worlds.step()
@@ -814,6 +913,11 @@ class Environment:
     def _weights_note(self):
         if not self.learners:
             return "as loaded / initialised -- reinlife_amd runs inference only, learn() is a no-op"
+        if self.learn == "reference":
+            frozen = [k for k in range(len(self.brains)) if k not in self.learners]
+            return ("brains %s trained on the device on the reference's own schedule and draws (learn='reference': per agent of the post-step "
+                    "list, when its age is a multiple of train_freq or it died; minibatches by random.sample over the replay deque)"
+                    % sorted(self.learners) + ("; brains %s as loaded / initialised (their kinds do not learn in this mode)" % frozen if frozen else ""))
         frozen = [k for k in range(len(self.brains)) if k not in self.learners]
         by = {name: [k for k in sorted(self.learners) if self.learners[k].spec is ENTRY[name]] for name in self._NOTES}
         note = []
@@ -962,7 +1066,10 @@ class Environment:
         and ONE rl_learn for all learners are queued on the same stream (learn_now) -- this build's schedule, not the reference's per-agent one."""
         if self.rng != "philox":
             for t in range(n_ticks):
-                self.act(n_epi + t); self.step(); self.update_env(n_epi + t)
+                self.act(n_epi + t); self.step()
+                if self.learn == "reference":
+                    self.learn_reference(n_epi + t)
+                self.update_env(n_epi + t)
             return
         interval = self.tracker.update_interval
         thr = -1 if self.refill_below is None else self.refill_below
@@ -1087,8 +1194,14 @@ def resolve_dist(dist=None):
     return None, 0, 1
 
 
-def warn_inference_only(frozen=None, kinds=("DQN",), draw=None):
+def warn_inference_only(frozen=None, kinds=("DQN",), draw=None, mode="device"):
     import warnings
+    if frozen is not None and mode == "reference":
+        warnings.warn("learn='reference' trains the %s brains of this run; brains %s are of other kinds: they stay inference only -- "
+                      "brain.learn() is a no-op for them and their weights are NOT updated (PERD3QN and PERDQN memories need their priorities on "
+                      "the host for the reference's draws: they do not train in this mode yet; learn='device' trains them on its own schedule)."
+                      % (", ".join(kinds[:-1]) + " and " + kinds[-1], ", ".join(frozen)), stacklevel=4)
+        return
     if frozen is not None:
         # (a line more only where learn_draw was given: every other run's message is what it was)
         drawn = "" if draw is None else "\nlearn_draw=%r draws the DQN / D3QN learners' minibatches by content-key rank (rl_learn_draw_rank)." % (draw,)
