@@ -207,7 +207,9 @@ int rl_bind_state(rl_world* h, const rl_state* device_ptrs);
  *   3  a world's agent list outgrew slot_cap                                 detail: slots
  *   4  a taped produce_choice outside [0, RL_N_BEST)                         detail: value
  *   5  rl_render: a world id outside [0, n_worlds) ([1] = the id)            detail: frame index
- *   6  rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo / rl_learn_td / rl_learn_td_wide: a minibatch slot outside [0, ring size) ([1] = brain index) detail: step, value */
+ *   6  rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo / rl_learn_td / rl_learn_td_wide: a minibatch slot outside [0, ring size) ([1] = brain index) detail: step, value
+ *   7  rl_learn_prioritized_choice: the priorities give no distribution -- all zero, a NaN or a negative one: where np.random.choice
+ *      raises ValueError ([1] = learner index)                               detail: rows of the memory, 0 */
 int rl_bind_error_flag(rl_world* h, int32_t* device_flag);
 
 /* tuning aid: device int64[32] receiving shader-clock stamps at the phase boundaries of world `world` (NULL = off) */
@@ -599,6 +601,69 @@ int rl_learn_prioritized_supported(int kind);
  * rl_learn, rl_learn_draw, rl_learn_dueling and the two older *_supported answers are unchanged by it. */
 int rl_learn_prioritized(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_prio* prios, int n_learners, int n_steps,
                          const int32_t* slots, void* stream);
+
+/* ---- the prioritised memory as the reference keeps it: store() and np.random.choice (PERD3QN, learn="reference") ------------------- */
+/* Two stream-ordered entry points, one launch of one workgroup per learner each, no allocation, no host round trip, at most
+ * RL_MAX_CAPTURE_BRAINS learners per call, kind RL_PERD3QN only (anything else: RL_E_UNSUPPORTED naming the kind).  They are draws, not
+ * learners: the update is rl_learn_prioritized, unchanged, on the slots rl_learn_prioritized_choice names.  In this use *prio_max and
+ * *seen of rl_prio are written by rl_learn_prioritized and read by nobody: the store takes its own maximum, over the live window.
+ *
+ * Notation.  C = the memory's capacity (PERD3QN.py:135); R >= C = the rows the ring holds (a caller that captures a whole tick's rows in
+ * front of the tick's train() calls needs R = C + slack, slack >= the rows of one tick).  Rows are numbered from 0 in storage order; row a
+ * sits in ring slot a % R and at the reference's memory index a % C.  rl_prio.priority is indexed by RING SLOT and holds R floats,
+ * zero-initialised.  Of rl_prio only `priority` (and, for the choice, `alpha`) is read. */
+typedef struct {
+    long long capacity;         /* C, in [1, 2^31) */
+    long long ring_rows;        /* R, in [C, 2^31) */
+    long long first_row;        /* a >= 0: the first row of the group */
+    long long n_rows;           /* m in [1, R - C]; anything else is RL_E_INVALID */
+} rl_prio_store;
+/* PrioritizedReplayBuffer.store (PERD3QN.py:143-155) for rows [a, a + m) of each learner:
+ *   M = 1.0f                                            when a == 0 (the first row of an empty memory)
+ *   M = max over rows r in [max(0, a - C), a) of priority[r % R]   otherwise, and, when a < C, of 0 (the memory indices no row has reached
+ *       yet count as np.max counts the array's unused zeros); a NaN in the window propagates, as np.max propagates it
+ *   priority[(a + j) % R] = M  for j < m
+ * A group gets ONE M.  That is the reference's result exactly when no train() lies inside the group: storing M never lowers the maximum
+ * (a row overwritten with the maximum keeps it), and only update_priorities changes it.  The caller cuts its groups at every train(). */
+int rl_learn_prioritized_store_ref(rl_world* h, const rl_learner* learners, const rl_prio* prios, const rl_prio_store* groups, int n_learners,
+                                   void* stream);
+#define RL_LEARN_CHOICE_MAX 64  /* the draws of one rl_learn_prioritized_choice call per learner at most */
+typedef struct {
+    long long capacity;         /* C, in [1, 2^31): slots and indices are int32 (a larger one is RL_E_INVALID naming this limit) */
+    long long ring_rows;        /* R, in [C, 2^31) */
+    long long stored;           /* rows stored so far, >= 1 (np.random.choice needs one row) */
+    int32_t batch;              /* in [1, RL_LEARN_CHOICE_MAX] */
+    const double* u;            /* device [batch]: the host's np.random.random_sample(batch), in [0,1) */
+    int32_t* indices;           /* device [batch]: the reference's memory indices */
+    int32_t* slots;             /* device [batch]: their ring slots, what rl_learn_prioritized takes */
+    double* bracket;            /* device [batch][2] or NULL: each draw's cdf[idx - 1] (0 for idx = 0) and cdf[idx] (tests, diagnostics) */
+    void* work;                 /* device, rl_learn_prioritized_choice_work_bytes(C) bytes of scratch: the cdf and the weights */
+} rl_prio_choice;
+/* the bytes of rl_prio_choice.work for a memory of `capacity` rows (0 for a capacity outside [1, 2^31)) */
+size_t rl_learn_prioritized_choice_work_bytes(long long capacity);
+/* PrioritizedReplayBuffer.sample's draw (PERD3QN.py:157-165) from host-drawn uniforms: np.random.choice(len, batch, p=probs) consumes
+ * exactly `batch` doubles of random_sample() and answers cdf.searchsorted(u, side="right"), cdf = probs.cumsum() in float64 divided by its
+ * last element.  Per learner, with T = 1024 and all sums taken left to right:
+ *   n       = min(stored, C)
+ *   a_i     = i + C * ((stored - 1 - i) / C)            (integer division) the row memory index i < n holds
+ *   p_i     = priority[a_i % R]
+ *   w_i     = (float)pow((double)p_i, (double)alpha)    alpha = 0.6f: probs ** self.alpha on a float32 array stays float32 under numpy 2
+ *   L       = ceil(n / T); chunk t = the indices [t L, min(n, (t + 1) L))
+ *   S       = (float)(sum over t = 0 .. T-1 of (sum over i in chunk t of (double)w_i))        both sums in double, rounded to float once
+ *   q_i     = w_i / S                                   in float
+ *   c_i     = sum over k in i's chunk, k <= i, of (double)q_k;    o_t = sum over t' < t of c_(last index of chunk t')
+ *   cdf_i   = (o_t + c_i) / (o_t + c_i at i = n - 1)    nondecreasing, cdf_(n-1) = 1.0
+ *   idx_j   = #{i : cdf_i <= u_j}                       side="right": a u on a boundary goes to the next row; a row of weight zero is never drawn
+ *   indices[j] = idx_j;  slots[j] = a_(idx_j) % R;  bracket[j] = {idx_j > 0 ? cdf_(idx_j - 1) : 0, cdf_(idx_j)}
+ * numpy's float32 power is within 1 ulp of w_i, not always equal to it, and its cumsum is sequential: the probabilities agree to a few
+ * float32 ulps and the cdf to about 2^-21, so a u that close to a boundary may name the neighbouring row.  The bits of indices, slots and
+ * bracket are the same in every run (no atomics, fixed association order).
+ * Refused on the device: where np.random.choice raises ValueError -- the weights sum to zero, or a priority is NaN or negative (or the sum
+ * overflows) -- the bound error flag gets code 7 and EVERY draw of that learner gets index 0 and slot a_0 % R; bracket is not written.
+ * Refused on the host (RL_E_INVALID naming the argument): stored < 1, batch outside [1, RL_LEARN_CHOICE_MAX], a null u / indices / slots /
+ * work, alpha <= 0, C or R outside their ranges. */
+int rl_learn_prioritized_choice(rl_world* h, const rl_learner* learners, const rl_prio* prios, const rl_prio_choice* draws, int n_learners,
+                                void* stream);
 
 /* ---- prioritised replay on wide minibatches (PERD3QN) ------------------------------------------------------------ */
 /* THIS BUILD'S OWN -- the reference trains one world on ONE minibatch of 64 per train() (PERD3QN.py:94-115).  rl_learn_prioritized_wide

@@ -20,7 +20,8 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
             limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None, seed=0, rng=None, per_agent_api=False,
             fused=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
             learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
-            learn_td_priority=None, learn_td_stamp=None, learn_ranks=None, learn_batch=None, learn_draw=None):
+            learn_td_priority=None, learn_td_stamp=None, learn_ranks=None, learn_reference_prioritized=None,
+            learn_batch=None, learn_draw=None):
     """Extra keyword-only arguments: n_worlds / device / seed / rng / synthetic_agents / refill_below (Environment); per_agent_api=True makes the reference's literal
     per-agent get_action / learn calls; fused (default: True for rng="philox" without per_agent_api) runs the loop through
     Environment.run -- whole chunks of ticks per launch, ending where the Tracker closes an interval -- instead of three launches
@@ -176,7 +177,18 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     float64 and one binary search per draw: independent draws with probability weight / sum, as the reference's np.random.choice(p=...),
     at any learn_batch["PERD3QN"], eight launches instead of two at a cost that does not grow with the batch.  {"PERDQN": "rank"}:
     rl_learn_td_draw_rank, the same STRATIFIED -- the total cut into 64 segments, one uniform per segment: the reference's Memory.sample(),
-    which the race draw cannot do.  Both are other samplers than the race draws: other rows, other parameters."""
+    which the race draw cannot do.  Both are other samplers than the race draws: other rows, other parameters.
+
+    learn_reference_prioritized (default None: learn="reference" is what it was, PERD3QN brains stay frozen and are named by its warning;
+    True needs learn="reference" and at least one Models.PERD3QN, ValueError before a device is touched): every PERD3QN brain trains on
+    the reference's schedule too -- PERD3QNAgent.learn (PERD3QN.py:117-125) has D3QNAgent.learn's shape.  Its priorities stay on the device,
+    one per row of a ring of capacity + slot_cap rows: the host draws np.random.random_sample(batch_size), exactly the doubles
+    np.random.choice(len, batch_size, p=probs) consumes, and three launches follow per train(): rl_learn_prioritized_store_ref (store()'s
+    maximum for the rows stored since the last stamp), rl_learn_prioritized_choice (the cdf walk, indices and slots staying on the device)
+    and rl_learn_prioritized on those slots.  np.random ends every tick in the reference's state.  The device's probabilities agree with
+    numpy's to a few float32 ulps, so a uniform within about 2^-21 of a cdf boundary may name the neighbouring row: with capacity=10000
+    that happens about once in some tens of train() calls, and a long run then leaves the reference's row choices while sampling the same
+    distribution.  PERDQN brains stay frozen and the warning names them."""
     if learn == "device" and (per_agent_api or fused is False):
         raise ValueError("trainer(learn='device') needs the fused path (fused=True, per_agent_api=False): the replay rings are filled "
                          "inside the multi-tick launches")
@@ -193,7 +205,8 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
                       device=device, seed=seed, rng=rng, synthetic_agents=synthetic_agents, refill_below=refill_below, dist=dist,
                       world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps, learn_kinds=learn_kinds,
                       learn_prioritized=learn_prioritized, learn_rollout=learn_rollout, rollout_steps=rollout_steps,
-                      learn_td_priority=learn_td_priority, learn_td_stamp=learn_td_stamp, learn_ranks=learn_ranks, learn_batch=learn_batch, learn_draw=learn_draw)
+                      learn_td_priority=learn_td_priority, learn_td_stamp=learn_td_stamp, learn_ranks=learn_ranks, learn_batch=learn_batch, learn_draw=learn_draw,
+                      learn_reference_prioritized=learn_reference_prioritized)
     env.reset()
     if fused is None:
         fused = env.rng == "philox" and not per_agent_api

@@ -164,7 +164,8 @@ class Environment:
                  pastel_colors=False, limit_reproduction=False, incentivize_killing=True, *, n_worlds=1, device=None,
                  seed=0, rng=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
                  learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
-                 learn_td_priority=None, learn_td_stamp=None, learn_ranks=None, learn_batch=None, learn_draw=None):
+                 learn_td_priority=None, learn_td_stamp=None, learn_ranks=None, learn_reference_prioritized=None,
+                 learn_batch=None, learn_draw=None):
         if not brains:
             raise ValueError("Environment needs a non-empty list of brains")
         if learn not in (None, "device", "reference"):
@@ -182,6 +183,17 @@ class Environment:
         # learn_prioritized=True: every PERD3QN brain trains through rl_learn_prioritized on a prioritised memory (PERD3QN.py:94-115,
         # 133-182).  A keyword of its own: learn_kinds and ENTRY_BY_METHOD answer what they answered.  Checked before a device is touched.
         self._opt_in("prioritized", learn_prioritized, learn, brains)
+        # learn_reference_prioritized=True: under learn="reference" every PERD3QN brain trains too -- its priorities stay on the device, the
+        # host draws np.random.choice's uniforms (rl_learn_prioritized_store_ref, rl_learn_prioritized_choice, then rl_learn_prioritized).
+        # A keyword of its own: without it learn="reference" is what it was.  Checked before a device is touched.
+        if learn_reference_prioritized not in (None, True):
+            raise ValueError("learn_reference_prioritized must be None or True, got %r" % (learn_reference_prioritized,))
+        if learn_reference_prioritized and learn != "reference":
+            raise ValueError("learn_reference_prioritized=True needs learn='reference' (got learn=%r)" % (learn,))
+        if learn_reference_prioritized and not any(getattr(b, "method", None) == "PERD3QN" for b in brains):
+            raise ValueError("learn_reference_prioritized=True needs at least one Models.PERD3QN brain (got %s)"
+                             % ", ".join(str(getattr(b, "method", b)) for b in brains))
+        self.learn_reference_prioritized = bool(learn_reference_prioritized)
         # learn_rollout=True: every PPO brain trains through rl_learn_ppo on rollouts drawn from the rows its current weights made
         # (PPO.py:71-77, 136-162).  A keyword of its own, like learn_prioritized.  Checked before a device is touched.
         self._opt_in("rollout", learn_rollout, learn, brains)
@@ -367,6 +379,7 @@ class Environment:
         self._ppo_narrow = {}       # ... and per PPO brain the rl_learn_ppo learner over the wide learner's tensors
         self._learned = False       # ... learn_reference() ran since the last step()
         self.reference_calls = []   # ... every Call made so far as (n_epi, Call), while log_reference_calls is on (tests, diagnostics)
+        self.reference_choices = []  # ... and per PERD3QN train() (n_epi, brain, indices, slots, bracket) as device tensors, likewise
         if learn == "reference":    # every condition is checked before a device is touched
             self._check_reference(brains, n_worlds, static_families, training, learn_every, steps_given)
         self.best_agents = []
@@ -469,10 +482,12 @@ class Environment:
         """The learners, rings and schedule of learn="reference" (learn_reference.py): a ring of the deque's maxlen + slot_cap rows per
         learning brain (the floor for the others, whose rows nobody reads), one DeviceLearner per DQN / D3QN / PPO brain whose packed
         tensor is the brain's acting weights from here on.  A PPO brain's learner is the wide one, built once for PPO_LIST_MAX rows; the
-        narrow entry's learner shares every tensor with it."""
-        from ..learn_reference import PPO_LIST_MAX, BrainSpec, ReferenceSchedule
+        narrow entry's learner shares every tensor with it.  With learn_reference_prioritized=True a PERD3QN brain gets a prioritised
+        learner (DeviceLearner(prioritized=True)) whose priorities, one per ring row, stay on the device."""
+        from ..learn_reference import KINDS, PPO_LIST_MAX, BrainSpec, ReferenceSchedule
         slack = _lib.slot_cap_for(max_agents)
-        self.schedule = ReferenceSchedule([BrainSpec.of(b) for b in brains], slack)
+        self.schedule = ReferenceSchedule([BrainSpec.of(b, prioritized=True) if self.learn_reference_prioritized else BrainSpec.of(b)
+                                           for b in brains], slack)
         specs = self.schedule.specs
         self.ring_floor = slack
         self.ring_rows = [self.schedule.ring_rows(k) if specs[k] else slack for k in range(len(brains))]
@@ -487,11 +502,13 @@ class Environment:
                 narrow = self._ppo_narrow[k] = DeviceLearner(brains[k], self.worlds.device, ring=ring, rollout=True)
                 for name in ("params", "adam_m", "adam_v", "state", "packed") + wide.spec.side_tensors:
                     setattr(narrow, name, getattr(wide, name))
+            elif s.method == "PERD3QN":
+                self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=ring, prioritized=True)
             else:
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=ring)
         frozen = ["%d (%s)" % (k, b.method) for k, b in enumerate(brains) if k not in self.learners]
         if frozen:
-            warn_inference_only(frozen, ("DQN", "D3QN", "PPO"), mode="reference")
+            warn_inference_only(frozen, KINDS, mode="reference_prioritized" if self.learn_reference_prioritized else "reference")
         if not self.learners:
             raise ValueError("learn='reference': none of the brains is of a kind that trains in this mode (DQN, D3QN, PPO)")
 
@@ -516,6 +533,10 @@ class Environment:
                 self.worlds.launches += 1
             elif c.kind == "ppo":
                 self._learn_ppo(c.brain, c.slots, c.wide)
+            elif c.kind == "store":   # PERD3QN: store()'s priority for the rows behind the tick's last train()
+                self.worlds.store_prioritized_reference([l], [self.schedule.specs[c.brain].capacity], [c.store[0]], [c.store[1]])
+            elif c.uniforms is not None:
+                self._learn_prioritized_reference(n_epi, c)
             else:
                 l.sync_target = bool(c.sync_target)
                 self.worlds.learn([l], c.slots.shape[0], slots=c.slots[None])
@@ -529,6 +550,18 @@ class Environment:
         l = self.learners[brain] if wide else self._ppo_narrow[brain]
         l.batch = int(np.asarray(slots).shape[-1])
         self.worlds.learn([l], 1, slots=np.asarray(slots, np.int32).reshape(1, 1, -1), gate=False)
+
+    def _learn_prioritized_reference(self, n_epi, c):
+        """One PERD3QNAgent.train() of learn_reference_prioritized=True: the stamp of the rows stored since the last one, the cdf walk on
+        the call's uniforms, and rl_learn_prioritized on the slots it leaves on the device -- three launches, nothing read back."""
+        l, capacity = self.learners[c.brain], self.schedule.specs[c.brain].capacity
+        self.worlds.store_prioritized_reference([l], [capacity], [c.store[0]], [c.store[1]])
+        indices, slots, bracket = self.worlds.choose_prioritized_reference([l], [capacity], [c.store[0] + c.store[1]], [c.uniforms],   # (the rows stored as of THIS call)
+                                                                           with_bracket=self.log_reference_calls)
+        l.sync_target = bool(c.sync_target)
+        self.worlds.learn([l], 1, slots=slots)
+        if self.log_reference_calls:
+            self.reference_choices.append((n_epi, c.brain, indices[0], slots[0, 0], bracket[0]))
 
     def _opt_in(self, keyword, value, learn, brains):
         """learn_<keyword>=True, the environment's spelling of DeviceLearner(..., <keyword>=True): None or True, with learn='device' and
@@ -915,9 +948,14 @@ class Environment:
             return "as loaded / initialised -- reinlife_amd runs inference only, learn() is a no-op"
         if self.learn == "reference":
             frozen = [k for k in range(len(self.brains)) if k not in self.learners]
+            prio = [k for k in sorted(self.learners) if self.learners[k].spec.family == "prioritized"]
             return ("brains %s trained on the device on the reference's own schedule and draws (learn='reference': per agent of the post-step "
                     "list, when its age is a multiple of train_freq or it died; minibatches by random.sample over the replay deque)"
-                    % sorted(self.learners) + ("; brains %s as loaded / initialised (their kinds do not learn in this mode)" % frozen if frozen else ""))
+                    % sorted(self.learners)
+                    + ("; the minibatches of brains %s by np.random.choice's rule on np.random's uniforms, the priorities kept and the cdf "
+                       "walked on the device (learn_reference_prioritized=True: rl_learn_prioritized_store_ref, rl_learn_prioritized_choice; a "
+                       "uniform within about 2^-21 of a cdf boundary may name the neighbouring row)" % prio if prio else "")
+                    + ("; brains %s as loaded / initialised (their kinds do not learn in this mode)" % frozen if frozen else ""))
         frozen = [k for k in range(len(self.brains)) if k not in self.learners]
         by = {name: [k for k in sorted(self.learners) if self.learners[k].spec is ENTRY[name]] for name in self._NOTES}
         note = []
@@ -1196,6 +1234,13 @@ def resolve_dist(dist=None):
 
 def warn_inference_only(frozen=None, kinds=("DQN",), draw=None, mode="device"):
     import warnings
+    if frozen is not None and mode == "reference_prioritized":
+        warnings.warn("learn='reference' with learn_reference_prioritized=True trains the %s and PERD3QN brains of this run; brains %s are of "
+                      "other kinds: they stay inference only -- brain.learn() is a no-op for them and their weights are NOT updated (a PERDQN "
+                      "memory's sum tree accumulates rounding in update order and append_sample makes forward passes per store: PERDQN brains do "
+                      "not train in this mode yet; learn='device' trains them on its own schedule)."
+                      % (", ".join(kinds), ", ".join(frozen)), stacklevel=4)
+        return
     if frozen is not None and mode == "reference":
         warnings.warn("learn='reference' trains the %s brains of this run; brains %s are of other kinds: they stay inference only -- "
                       "brain.learn() is a no-op for them and their weights are NOT updated (PERD3QN and PERDQN memories need their priorities on "

@@ -74,6 +74,15 @@ class Prio(C.Structure):  # rl_prio
     _fields_ = [(n, C.c_void_p) for n in ("priority", "weight", "keys", "prio_max", "seen")] + [("alpha", C.c_float)]
 
 
+class PrioStore(C.Structure):  # rl_prio_store
+    _fields_ = [(n, C.c_longlong) for n in ("capacity", "ring_rows", "first_row", "n_rows")]
+
+
+class PrioChoice(C.Structure):  # rl_prio_choice
+    _fields_ = ([(n, C.c_longlong) for n in ("capacity", "ring_rows", "stored")] + [("batch", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("u", "indices", "slots", "bracket", "work")])
+
+
 class Ppo(C.Structure):  # rl_ppo
     _fields_ = [("lmbda", C.c_float), ("eps_clip", C.c_float), ("k_epoch", C.c_int32)] + [(n, C.c_void_p) for n in ("seen", "fresh", "keys")]
 
@@ -98,6 +107,8 @@ LEARN_TD_STAMP_LAUNCHES = 2   # RL_LEARN_TD_STAMP_LAUNCHES: the launches of one 
 PPO_ROLLOUT_MAX = 32   # RL_PPO_ROLLOUT_MAX: the rows of a rollout at most (rl_learn_ppo)
 LEARN_PPO_WIDE_MAX = 2048   # RL_LEARN_PPO_WIDE_MAX: the rows of a rollout at most (rl_learn_ppo_wide)
 LEARN_TD_WIDE_MAX = 2048   # RL_LEARN_TD_WIDE_MAX: the rows of a minibatch at most (rl_learn_td_wide)
+LEARN_CHOICE_MAX = 64   # RL_LEARN_CHOICE_MAX: the draws of one rl_learn_prioritized_choice call per learner at most
+ERR_NO_DISTRIBUTION = 7   # error-flag code: rl_learn_prioritized_choice found priorities np.random.choice would refuse
 
 
 class Brain(C.Structure):
@@ -151,6 +162,9 @@ ABI = [
     ("rl_learn_prioritized_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Prio), C.c_int, C.c_int, _P, _P]),
     ("rl_learn_prioritized_supported", C.c_int, [C.c_int]),
     ("rl_learn_prioritized", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Prio), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_prioritized_store_ref", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Prio), C.POINTER(PrioStore), C.c_int, _P]),
+    ("rl_learn_prioritized_choice_work_bytes", C.c_size_t, [C.c_longlong]),
+    ("rl_learn_prioritized_choice", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Prio), C.POINTER(PrioChoice), C.c_int, _P]),
     ("rl_learn_prioritized_wide_supported", C.c_int, [C.c_int]),
     ("rl_learn_prioritized_wide_work_bytes", C.c_size_t, [C.c_int, C.c_int]),
     ("rl_learn_prioritized_wide_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(Prio), C.c_int, C.c_int, _P, _P]),

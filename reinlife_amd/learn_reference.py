@@ -24,6 +24,16 @@ most rows one tick appends (slot_cap).  At an agent's call with c rows stored, l
 slot (c - len + i) % (C + slack) (deque_slots): every such row is still in the ring at the end of the tick.  A PPO list lives in a ring
 of PPO_LIST_MAX + slack rows and may not grow beyond PPO_LIST_MAX rows (ValueError).
 
+  PERD3QN (PERD3QN.py:117-125, 143-165; only where the caller opts in, BrainSpec.of(brain, prioritized=True))   D3QN's shape: store; once
+       n_epi > exploration: on the trigger one update on np.random.choice(len, batch_size, p=probs) -- WITH replacement, so one row is
+       enough and no size error is raised -- then the same target copies.  np.random.choice consumes exactly batch_size doubles of
+       np.random.random_sample whatever p is: the Call carries u = np.random.random_sample(batch_size), the only draw made here (nothing
+       comes from `random`), and the device walks the cdf of the priorities it keeps (rl_learn_prioritized_choice): `slots` and `indices`
+       are None, they are the device's.  store() gives a new row the priorities' maximum AS OF THAT STORE and only train() changes the
+       maximum, so the rows stored since the last stamp are stamped as one group in front of every train() (`store`, rows
+       [first, first + count)), and a tick that stored rows ends with a Call of kind "store" for those not yet stamped: no group spans a
+       train() and none exceeds the rows of one tick, that is `slack` rows.
+
 Brains of other kinds are not scheduled: their rows are counted by nobody here and they make no draws."""
 import random
 from typing import NamedTuple
@@ -34,13 +44,17 @@ DQN_CAPACITY, DQN_BATCH, DQN_STEPS, DQN_GATE = 50_000, 32, 5, 1000   # DQN.py:15
 PPO_LIST_MAX = 2048      # the rows of the longest PPO list a call can train on (rl_learn_ppo_wide's batch limit)
 PPO_NARROW_MAX = 32      # up to here a list goes to rl_learn_ppo, beyond to rl_learn_ppo_wide
 KINDS = ("DQN", "D3QN", "PPO")   # the brain methods this schedule trains
+OPT_IN_KINDS = ("PERD3QN",)      # ... and those it trains where the caller asks for it (BrainSpec.of(brain, prioritized=True))
 
 
 class Call(NamedTuple):
     """One device call of a tick.  kind "learn": n_steps minibatch updates (DQN 5, D3QN 1) on the ring slots `slots` [n_steps][batch],
     then the target copy iff sync_target.  kind "sync": params -> target, no update (D3QN).  kind "ppo": one PPO.learn() on the rows at
     `slots` [1][length], wide iff the list is longer than PPO_NARROW_MAX.  `size` is the deque's (list's) length at the call and
-    `indices` what random.sample drew, as deque indices [n_steps][batch] (PPO, sync: None)."""
+    `indices` what random.sample drew, as deque indices [n_steps][batch] (PPO, sync: None).
+    PERD3QN: kind "learn" carries `uniforms` [batch] float64 -- np.random.choice's doubles, for the device's cdf walk; slots and indices
+    are None -- and `store` = (first row, rows): the group store() stamps in front of that train(); `size` is len(memory).  kind
+    "store": the stamp alone, of the rows a tick stored behind its last train()."""
     kind: str
     brain: int
     slots: np.ndarray = None
@@ -48,6 +62,8 @@ class Call(NamedTuple):
     size: int = 0
     indices: np.ndarray = None
     wide: bool = False
+    uniforms: np.ndarray = None
+    store: tuple = None
 
 
 class BrainSpec(NamedTuple):
@@ -59,8 +75,9 @@ class BrainSpec(NamedTuple):
     soft_update_freq: int = 1
 
     @classmethod
-    def of(cls, brain):
-        """The spec of a brain object by its own attributes, or None for a kind this schedule does not train."""
+    def of(cls, brain, prioritized=False):
+        """The spec of a brain object by its own attributes, or None for a kind this schedule does not train.  prioritized=True: a
+        PERD3QN brain gets a spec too (Environment's learn_reference_prioritized=True)."""
         method, freq = getattr(brain, "method", None), int(getattr(brain, "train_freq", 20))
         if method == "DQN":
             return cls("DQN", freq)
@@ -68,7 +85,21 @@ class BrainSpec(NamedTuple):
             return cls("D3QN", freq, int(brain.capacity), int(brain.batch_size), int(brain.exploration), int(brain.soft_update_freq))
         if method == "PPO":
             return cls("PPO", freq, PPO_LIST_MAX, 0)
+        if method == "PERD3QN" and prioritized:
+            return cls("PERD3QN", freq, int(brain.capacity), int(brain.batch_size), int(brain.exploration), int(brain.soft_update_freq))
         return None
+
+
+def memory_rows(stored, capacity, indices):
+    """The rows PrioritizedReplayBuffer.memory holds at `indices` once `stored` rows were stored (PERD3QN.py:149-155: row a is written to
+    index a % capacity): index i holds the latest such row, i + capacity * ((stored - 1 - i) // capacity)."""
+    i = np.asarray(indices, np.int64)
+    return i + int(capacity) * ((int(stored) - 1 - i) // int(capacity))
+
+
+def memory_slots(stored, capacity, ring_rows, indices):
+    """... and the ring slots they sit in: row a is in slot a % ring_rows (rl_learn_prioritized_choice's `slots`)."""
+    return (memory_rows(stored, capacity, indices) % int(ring_rows)).astype(np.int32)
 
 
 def deque_slots(stored, capacity, ring_rows, indices):
@@ -86,12 +117,13 @@ class ReferenceSchedule:
         if self.slack < 1:
             raise ValueError("ReferenceSchedule: slack must be >= 1 (the most rows one tick appends to a ring), got %r" % (slack,))
         for s in self.specs:
-            if s is not None and s.method not in KINDS:
+            if s is not None and s.method not in KINDS + OPT_IN_KINDS:
                 raise ValueError("ReferenceSchedule trains %s brains, not %s" % (", ".join(KINDS), s.method))
         n = len(self.specs)
         self.stored = [0] * n        # rows stored so far, per brain
         self.listed = [0] * n        # PPO: the row the current list starts at
-        self.stale = [False] * n     # D3QN: an update was made since the last eval -> target copy
+        self.stale = [False] * n     # D3QN, PERD3QN: an update was made since the last eval -> target copy
+        self.stamped = [0] * n       # PERD3QN: the rows whose priority store() has been queued for
         self.calls = 0               # Calls handed out so far
 
     def ring_rows(self, brain):
@@ -120,6 +152,9 @@ class ReferenceSchedule:
             self.stored[b] += 1                                   # memorize() / put_data()
             trigger = age % s.train_freq == 0 or dead
             out += getattr(self, "_" + s.method.lower())(b, s, n_epi, trigger)
+        for b in sorted(per_brain):                               # PERD3QN: the rows stored behind the tick's last train()
+            if self.specs[b].method == "PERD3QN" and self.stamped[b] < self.stored[b]:
+                out.append(Call("store", b, store=self._store_group(b)))
         self.calls += len(out)
         return out
 
@@ -145,6 +180,23 @@ class ReferenceSchedule:
             size, idx, slots = self._sample(b, s, 1)
             self.stale[b] = not sync
             return [Call("learn", b, slots, sync, size, idx)]
+        if sync and self.stale[b]:
+            self.stale[b] = False
+            return [Call("sync", b)]
+        return []
+
+    def _store_group(self, b):
+        first, self.stamped[b] = self.stamped[b], self.stored[b]
+        return (first, self.stored[b] - first)
+
+    def _perd3qn(self, b, s, n_epi, trigger):
+        if n_epi <= s.exploration:                                # PERD3QN.py:120
+            return []
+        sync = n_epi % s.soft_update_freq == 0                    # PERD3QN.py:124-125: after every such agent call
+        if trigger:
+            u = np.random.random_sample(s.batch)                  # np.random.choice(len, batch, p=probs): these doubles, nothing else
+            self.stale[b] = not sync
+            return [Call("learn", b, None, sync, self.size(b), None, False, u, self._store_group(b))]
         if sync and self.stale[b]:
             self.stale[b] = False
             return [Call("sync", b)]

@@ -253,7 +253,9 @@ class DeviceWorlds:
     @staticmethod
     def raise_on_error_flag(e):
         if e[0] != 0:
-            raise _lib.ReinLifeHipError("device error flag: code %d world %d detail (%d, %d)" % tuple(int(x) for x in e))
+            hint = (" -- rl_learn_prioritized_choice: the priorities of learner [world] give no distribution (all zero, a NaN or a negative "
+                    "one), where np.random.choice raises ValueError") if int(e[0]) == _lib.ERR_NO_DISTRIBUTION else ""
+            raise _lib.ReinLifeHipError("device error flag: code %d world %d detail (%d, %d)" % tuple(int(x) for x in e) + hint)
 
     def readback(self, tensors):
         """Small device tensors on their way to pinned host memory BEHIND everything queued on the current stream so far and NEXT TO
@@ -562,6 +564,57 @@ class DeviceWorlds:
         sides = (_lib.TdPrio * n)(*[l.side_struct(_lib.TdPrio) for l in learners])
         _lib.check(self.lib.rl_learn_td_stamp(self.handle, arr, rings, sides, n, self._stream()), "rl_learn_td_stamp")
         self.launches += _lib.LEARN_TD_STAMP_LAUNCHES
+
+    def _reference_prio_args(self, who, learners):
+        n = len(learners)
+        if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
+            raise ValueError("%s(): 1 to %d learners per call (got %d)" % (who, _lib.MAX_CAPTURE_BRAINS, n))
+        if any(l.spec.side is not _lib.Prio for l in learners):
+            raise ValueError("%s(): every learner must be a prioritised one (DeviceLearner(..., prioritized=True))" % who)
+        return n, (_lib.Learner * n)(*[l.struct() for l in learners]), (_lib.Prio * n)(*[l.side_struct(_lib.Prio) for l in learners])
+
+    def store_prioritized_reference(self, learners, capacities, first_rows, n_rows):
+        """PrioritizedReplayBuffer.store's priority rule (PERD3QN.py:143-155) as learn="reference" uses it (rl_learn_prioritized_store_ref,
+        one launch, queued on the current stream): for learner i the rows [first_rows[i], first_rows[i] + n_rows[i]) -- numbered from 0 in
+        storage order, row a in slot a % ring rows of learner.priority -- get the maximum of the priorities of the capacities[i] rows in
+        front of them (1.0 into an empty memory).  One maximum per group: the reference's result where no train() lies inside it.
+        n_rows[i] at most ring rows - capacities[i]."""
+        n, arr, sides = self._reference_prio_args("store_prioritized_reference", learners)
+        groups = (_lib.PrioStore * n)(*[_lib.PrioStore(int(c), int(l.ring["state"].shape[0]), int(a), int(m))
+                                        for l, c, a, m in zip(learners, capacities, first_rows, n_rows)])
+        _lib.check(self.lib.rl_learn_prioritized_store_ref(self.handle, arr, sides, groups, n, self._stream()), "rl_learn_prioritized_store_ref")
+        self.launches += 1
+
+    def choose_prioritized_reference(self, learners, capacities, stored, uniforms, with_bracket=False):
+        """PrioritizedReplayBuffer.sample's np.random.choice (PERD3QN.py:157-165) from uniforms the host has drawn
+        (rl_learn_prioritized_choice, one launch, queued on the current stream): learner i's memory of capacities[i] rows, stored[i] rows
+        stored so far, priorities in learner.priority by ring slot; uniforms[i] = np.random.random_sample(batch), all of one batch <= 64.
+        Returns device tensors: indices int32 [n, batch] (the reference's memory indices), slots int32 [n, 1, batch] (what
+        learn(learners, 1, slots=...) takes) and, with_bracket=True, each draw's cdf[idx - 1] and cdf[idx] as float64 [n, batch, 2] (else
+        None).  Priorities np.random.choice would refuse (all zero, a NaN) set the error flag, code _lib.ERR_NO_DISTRIBUTION.  Keeps
+        learner.choice_work (scratch) on the learners, allocated once per capacity."""
+        n, arr, sides = self._reference_prio_args("choose_prioritized_reference", learners)
+        u = np.ascontiguousarray(np.asarray(uniforms, np.float64).reshape(n, -1))
+        batch = u.shape[1]
+        if not 1 <= batch <= _lib.LEARN_CHOICE_MAX:
+            raise ValueError("choose_prioritized_reference(): 1 to %d uniforms per learner (got %d)" % (_lib.LEARN_CHOICE_MAX, batch))
+        for l, c in zip(learners, capacities):
+            need = int(self.lib.rl_learn_prioritized_choice_work_bytes(int(c)))
+            if need < 1:
+                raise ValueError("choose_prioritized_reference(): capacity must be in [1, 2^31) (got %r)" % (c,))
+            if getattr(l, "choice_work", None) is None or l.choice_work.numel() != need:
+                l.choice_work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        u_dev = torch.as_tensor(u, device=self.device)
+        indices = torch.zeros((n, batch), dtype=torch.int32, device=self.device)
+        slots = torch.zeros((n, 1, batch), dtype=torch.int32, device=self.device)
+        bracket = torch.zeros((n, batch, 2), dtype=torch.float64, device=self.device) if with_bracket else None
+        draws = (_lib.PrioChoice * n)(*[_lib.PrioChoice(int(c), int(l.ring["state"].shape[0]), int(s), batch, _ptr(u_dev[i]), _ptr(indices[i]),
+                                                        _ptr(slots[i]), _ptr(bracket[i]) if with_bracket else None, _ptr(l.choice_work))
+                                        for i, (l, c, s) in enumerate(zip(learners, capacities, stored))])
+        _lib.check(self.lib.rl_learn_prioritized_choice(self.handle, arr, sides, draws, n, self._stream()), "rl_learn_prioritized_choice")
+        self._choice_keep = u_dev   # (the launch reads the uniforms asynchronously)
+        self.launches += 1
+        return indices, slots, bracket
 
     def _draw_side_rank(self, who, draw, learners, n_steps, stratified, side, one_of):
         """draw_prioritized_rank / draw_td_rank: the C entry `draw`, fed the learners' side structs and their order / cum / work buffers.
