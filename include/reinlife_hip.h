@@ -557,7 +557,8 @@ typedef struct {
  * for n_learners PERD3QN brains, stream-ordered, no host round trip, no allocation; like rl_learn_draw it does not depend on the slots
  * the rings' rows sit in.  Two launches:
  *   prepare   per row of [0, size): the slots in [*seen, *ring.count) mod capacity (all of them when count - seen >= capacity) get
- *             priority = *prio_max; weight = powf(priority, alpha); keys[row] = the row's content key exactly as rl_learn_draw makes it
+ *             priority = *prio_max; weight = powf(priority, alpha) (alpha == 1: the priority itself, bit for bit); keys[row] = the
+ *             row's content key exactly as rl_learn_draw makes it
  *   pick      one workgroup per draw d = s * batch + j (batch in [1,64] directly): v = mix64(key ^ salt_d), salt_d = words 0-1 of
  *             rl_philox(seed, 0, i, (uint32)state[1], RL_SITE_LEARN_PRIO, d); U = ((v >> 41) + 0.5) / 2^23, a uniform in (0,1);
  *             t = -logf(U) / weight; the draw takes the row with the smallest (t, v, slot), compared lexicographically.  An exponential

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void k_prio_prepare(const PrioArgs A)
             float p;
             if (stamp) { p = *B.prio_max; B.priority[row] = p; }
             else p = B.priority[row];
-            B.weight[row] = powf(p, B.alpha);
+            B.weight[row] = B.alpha == 1.0f ? p : powf(p, B.alpha);   // (the device powf(p, 1.0f) is up to 1 ulp off p)
         }
         B.keys[row] = k;
     }
