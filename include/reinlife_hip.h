@@ -209,7 +209,11 @@ int rl_bind_state(rl_world* h, const rl_state* device_ptrs);
  *   5  rl_render: a world id outside [0, n_worlds) ([1] = the id)            detail: frame index
  *   6  rl_learn / rl_learn_dueling / rl_learn_prioritized / rl_learn_ppo / rl_learn_td / rl_learn_td_wide: a minibatch slot outside [0, ring size) ([1] = brain index) detail: step, value
  *   7  rl_learn_prioritized_choice: the priorities give no distribution -- all zero, a NaN or a negative one: where np.random.choice
- *      raises ValueError ([1] = learner index)                               detail: rows of the memory, 0 */
+ *      raises ValueError ([1] = learner index)                               detail: rows of the memory, 0
+ *   8  rl_learn_td_tree_sample: a draw ended on a leaf no row has reached, where Memory.sample draws again -- detail: the draw, the
+ *      leaf's memory index; or the tree's total is not a positive finite number -- detail: -1, 0 ([1] = learner index)
+ *   9  rl_learn_td_tree_update: a leaf index outside the tree's leaves or a slot outside the ring ([1] = learner index)
+ *                                                                             detail: position in the batch, the leaf index */
 int rl_bind_error_flag(rl_world* h, int32_t* device_flag);
 
 /* tuning aid: device int64[32] receiving shader-clock stamps at the phase boundaries of world `world` (NULL = off) */
@@ -977,6 +981,81 @@ int rl_learn_td_stamp(rl_world* h, const rl_learner* learners, const rl_replay* 
  * Every older entry point and *_supported answer is unchanged by it (they refuse RL_PERDQN). */
 int rl_learn_td(rl_world* h, const rl_learner* learners, const rl_replay* rings, const rl_tdprio* tds, int n_learners, int n_steps,
                 const int32_t* slots, void* stream);
+
+/* ---- the sum tree as the reference keeps it: Memory.add, Memory.sample, Memory.update (PERDQN, learn="reference") ------------------ */
+/* Three stream-ordered entry points, one launch of one workgroup per learner each, no allocation, no host round trip, no float atomics,
+ * at most RL_MAX_CAPTURE_BRAINS learners per call, kind RL_PERDQN only (anything else: RL_E_UNSUPPORTED naming the kind).  They keep the
+ * memory, not the network: the update is rl_learn_td, unchanged, on the slots rl_learn_td_tree_sample names (min_size = 0: the caller
+ * gates at train_start), and rl_learn_td_tree_update follows it.  Of rl_tdprio only `priority` and `p_new` are read.
+ *
+ * Notation.  C = the memory's capacity (Memory.capacity, PERDQN.py:269-271), in [2, 2^30]: SumTree._propagate (:209-215) never ends for
+ * C = 1, whose only leaf is the root, and tree indices are int32 (anything else: RL_E_INVALID naming the capacity).  R >= C = the rows
+ * the ring holds, R < 2^31 (a caller that captures a whole tick's rows in front of the tick's train_model() calls needs R = C + slack,
+ * slack >= the rows of one tick).  Rows are numbered from 0 in storage order; row a sits in ring slot a % R and at the reference's memory
+ * index a % C.  rl_tdprio.priority is indexed by RING SLOT and holds R floats.  `tree` is a caller-owned device double[2 C - 1] per
+ * learner, zero-initialised, in the reference's layout: the leaf of memory index j at j + C - 1, the parent of node i at (i - 1) / 2.
+ * update(i, p) below is SumTree.update (:248-252): change = p - tree[i]; tree[i] = p; then tree[k] = tree[k] + change for every proper
+ * ancestor k of i, up to the root -- each a separately rounded double operation.  update32(i, p) is the same loop as the reference runs
+ * it when p is a float32 torch scalar, which is how append_sample's priority arrives (PERDQN.py:126-128, 273-278): change =
+ * (float)p - (float)tree[i] in float; tree[i] = p; tree[k] = (double)((float)tree[k] + change), the node rounded to float, the sum taken
+ * in float.  Inner nodes on the path of a stored row therefore hold float32 values until an update batch touches them.
+ * Between calls, for every row the memory holds: priority[row % R] == (float)tree[its leaf]; leaves only ever hold float32 values.
+ * The bits of `tree` and `priority` are those of the reference's sequential loop over the same updates, in every run: change depends
+ * only on the earlier updates of the same leaf and every inner node receives its changes in update order, so each node's final value
+ * is computed by one thread walking the node's own subsequence of the list (rl_learn_td_ref.hip). */
+typedef struct {
+    double* tree;               /* device [2 C - 1] */
+    long long capacity;         /* C, in [2, 2^30] */
+    long long ring_rows;        /* R, in [C, 2^31) */
+    long long first_row;        /* a >= 0: the first row of the group */
+    long long n_rows;           /* m in [1, R - C]; anything else is RL_E_INVALID */
+} rl_td_tree_store;
+/* Memory.add (PERDQN.py:276-278, 234-245) for rows [a, a + m) of each learner, in row order: update32((a + j) % C + C - 1, p_new)
+ * and priority[(a + j) % R] = p_new.  append_sample's error is exactly 0 (rl_tdprio, point 1), so p_new is every stored row's priority
+ * and storing a row needs no forward pass. */
+int rl_learn_td_tree_store(rl_world* h, const rl_learner* learners, const rl_tdprio* tds, const rl_td_tree_store* groups, int n_learners,
+                           void* stream);
+#define RL_LEARN_TD_TREE_BATCH_MAX 64  /* the draws of one rl_learn_td_tree_sample call, the updates of one rl_learn_td_tree_update call, per learner at most */
+typedef struct {
+    const double* tree;         /* device [2 C - 1] */
+    long long capacity;         /* C, in [2, 2^30] */
+    long long ring_rows;        /* R, in [C, 2^31) */
+    long long stored;           /* rows stored so far, >= 1 */
+    int32_t n;                  /* the draws, in [1, RL_LEARN_TD_TREE_BATCH_MAX] */
+    const double* u;            /* device [n]: the host's random.random() draws, in [0,1) */
+    int32_t* idxs;              /* device [n]: TREE indices (the reference's idxs), in [C - 1, 2 C - 1) */
+    int32_t* slots;             /* device [n]: the ring slots of the rows those leaves hold, what rl_learn_td takes */
+    double* s;                  /* device [n] or NULL: each draw's point s_i (tests, diagnostics) */
+    double* leaves;             /* device [n] or NULL: tree[idxs[i]] (tests, diagnostics) */
+} rl_td_tree_sample;
+/* Memory.sample(n)'s draw (PERDQN.py:280-298) from host-drawn uniforms, random.uniform(a, b) being a + (b - a) * random.random().  Per
+ * learner, one thread per draw i, every operation a separately rounded double:
+ *   segment = tree[0] / n;  a_i = segment * i;  b_i = segment * (i + 1);  s_i = a_i + (b_i - a_i) * u_i
+ *   _retrieve: k = 0; while 2 k + 1 < 2 C - 1: left = 2 k + 1; if s <= tree[left]: k = left, else: s = s - tree[left], k = left + 1
+ *   idxs[i] = k;  j = k - (C - 1);  slots[i] = (j + C * ((stored - 1 - j) / C)) % R  (integer division: the latest row at memory index j)
+ *   s[i] = s_i (as drawn, before the walk) and leaves[i] = tree[k], where given
+ * Refused on the device with error-flag code 8: a draw with j >= min(stored, C) -- a leaf no row has reached, where the reference's
+ * `while True` (:291-295) draws again from a generator the device does not have -- or a total that is not a positive finite number.
+ * EVERY draw of that learner then gets idxs = C - 1 and the slot of memory index 0; s and leaves are not written; the other learners of
+ * the call are untouched.  The run has then left the reference's draw order.
+ * Refused on the host (RL_E_INVALID naming the argument): stored < 1, n outside its range, a null tree / u / idxs / slots, C or R
+ * outside their ranges. */
+int rl_learn_td_tree_sample(rl_world* h, const rl_learner* learners, const rl_tdprio* tds, const rl_td_tree_sample* draws, int n_learners,
+                            void* stream);
+typedef struct {
+    double* tree;               /* device [2 C - 1] */
+    long long capacity;         /* C, in [2, 2^30] */
+    long long ring_rows;        /* R, in [C, 2^31) */
+    int32_t n;                  /* the updates, in [1, RL_LEARN_TD_TREE_BATCH_MAX] */
+    const int32_t* idxs;        /* device [n]: tree indices, as rl_learn_td_tree_sample wrote them */
+    const int32_t* slots;       /* device [n]: their ring slots */
+} rl_td_tree_update;
+/* train_model's loop (PERDQN.py:175-177) behind rl_learn_td, which has rewritten priority[slots[i]]: for i = 0 .. n - 1 in order,
+ * update(idxs[i], (double)priority[slots[i]]).  A leaf named twice gets equal bits twice: its second change is 0.  An idxs[i] outside
+ * [C - 1, 2 C - 1) or a slots[i] outside [0, R) is skipped and sets error-flag code 9. */
+int rl_learn_td_tree_update(rl_world* h, const rl_learner* learners, const rl_tdprio* tds, const rl_td_tree_update* batches, int n_learners,
+                            void* stream);
+
 /* THIS BUILD'S OWN -- the reference trains one world on ONE minibatch of 64 per train_model() (PERDQN.py:130-186).  rl_learn_td_wide is
  * rl_learn_td on a minibatch of 1 .. RL_LEARN_TD_WIDE_MAX rows, computed in 64-row tiles with one 512-thread workgroup per (learner,
  * tile).  The rows of a step meet in two scalars, p_min and mean(is_w), both over the WHOLE batch, and the tiles rewrite the priorities

@@ -21,7 +21,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
             fused=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
             learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
             learn_td_priority=None, learn_td_stamp=None, learn_ranks=None, learn_reference_prioritized=None,
-            learn_batch=None, learn_draw=None):
+            learn_reference_td=None, learn_batch=None, learn_draw=None):
     """Extra keyword-only arguments: n_worlds / device / seed / rng / synthetic_agents / refill_below (Environment); per_agent_api=True makes the reference's literal
     per-agent get_action / learn calls; fused (default: True for rng="philox" without per_agent_api) runs the loop through
     Environment.run -- whole chunks of ticks per launch, ending where the Tracker closes an interval -- instead of three launches
@@ -188,7 +188,20 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
     and rl_learn_prioritized on those slots.  np.random ends every tick in the reference's state.  The device's probabilities agree with
     numpy's to a few float32 ulps, so a uniform within about 2^-21 of a cdf boundary may name the neighbouring row: with capacity=10000
     that happens about once in some tens of train() calls, and a long run then leaves the reference's row choices while sampling the same
-    distribution.  PERDQN brains stay frozen and the warning names them."""
+    distribution.  PERDQN brains stay frozen and the warning names them.
+
+    learn_reference_td (default None: learn="reference" is what it was, with or without learn_reference_prioritized, and PERDQN brains stay
+    frozen; True needs learn="reference" and at least one Models.PERDQN, ValueError before a device is touched): every PERDQN brain trains
+    on the reference's schedule too -- PERDQNAgent.learn (PERDQN.py:188-195): store; on the trigger, once the memory holds train_start
+    rows, one train_model() and the target copy.  The memory's sum tree stays on the device as float64 [2 capacity - 1] in the
+    reference's layout and with the reference's rounding: every node ends with the bits the reference's sequential update loop gives it.
+    The host draws [random.random() for _ in range(batch_size)], the doubles Memory.sample's random.uniform calls consume, and four
+    launches follow per train_model(): rl_learn_td_tree_store (the rows stored since the last group, each with append_sample's constant
+    priority), rl_learn_td_tree_sample (the stratified walk; tree indices and ring slots stay on the device), rl_learn_td on those slots,
+    rl_learn_td_tree_update.  brain.epsilon loses epsilon_decay per train_model() while above epsilon_min, on the host, so act()'s coins
+    follow the reference.  `random` ends every tick in the reference's state as long as no draw lands on a leaf no row has reached --
+    there the reference draws again, which the host cannot know: the device sets error-flag code 8 and trainer() raises at the end of the
+    loop."""
     if learn == "device" and (per_agent_api or fused is False):
         raise ValueError("trainer(learn='device') needs the fused path (fused=True, per_agent_api=False): the replay rings are filled "
                          "inside the multi-tick launches")
@@ -206,7 +219,7 @@ def trainer(brains, n_episodes=10_000, width=30, height=30, visualize_results=Fa
                       world_base=world_base, learn=learn, learn_every=learn_every, learn_steps=learn_steps, learn_kinds=learn_kinds,
                       learn_prioritized=learn_prioritized, learn_rollout=learn_rollout, rollout_steps=rollout_steps,
                       learn_td_priority=learn_td_priority, learn_td_stamp=learn_td_stamp, learn_ranks=learn_ranks, learn_batch=learn_batch, learn_draw=learn_draw,
-                      learn_reference_prioritized=learn_reference_prioritized)
+                      learn_reference_prioritized=learn_reference_prioritized, learn_reference_td=learn_reference_td)
     env.reset()
     if fused is None:
         fused = env.rng == "philox" and not per_agent_api

@@ -165,7 +165,7 @@ class Environment:
                  seed=0, rng=None, synthetic_agents=None, refill_below=None, dist=None, world_base=None, learn=None, learn_every=None,
                  learn_steps=5, learn_kinds=None, learn_prioritized=None, learn_rollout=None, rollout_steps=1,
                  learn_td_priority=None, learn_td_stamp=None, learn_ranks=None, learn_reference_prioritized=None,
-                 learn_batch=None, learn_draw=None):
+                 learn_reference_td=None, learn_batch=None, learn_draw=None):
         if not brains:
             raise ValueError("Environment needs a non-empty list of brains")
         if learn not in (None, "device", "reference"):
@@ -194,6 +194,23 @@ class Environment:
             raise ValueError("learn_reference_prioritized=True needs at least one Models.PERD3QN brain (got %s)"
                              % ", ".join(str(getattr(b, "method", b)) for b in brains))
         self.learn_reference_prioritized = bool(learn_reference_prioritized)
+        # learn_reference_td=True: under learn="reference" every PERDQN brain trains too -- its sum tree stays on the device in float64 with
+        # the reference's rounding order, the host draws Memory.sample's uniforms (rl_learn_td_tree_store, rl_learn_td_tree_sample,
+        # rl_learn_td, rl_learn_td_tree_update).  A keyword of its own: learn_reference_prioritized=True leaves PERDQN brains frozen, as it
+        # did.  Checked before a device is touched.
+        if learn_reference_td not in (None, True):
+            raise ValueError("learn_reference_td must be None or True, got %r" % (learn_reference_td,))
+        if learn_reference_td and learn != "reference":
+            raise ValueError("learn_reference_td=True needs learn='reference' (got learn=%r)" % (learn,))
+        if learn_reference_td and not any(getattr(b, "method", None) == "PERDQN" for b in brains):
+            raise ValueError("learn_reference_td=True needs at least one Models.PERDQN brain (got %s)"
+                             % ", ".join(str(getattr(b, "method", b)) for b in brains))
+        if learn_reference_td:
+            small = [int(b.memory_size) for b in brains if getattr(b, "method", None) == "PERDQN" and int(b.memory_size) < 2]
+            if small:
+                raise ValueError("learn_reference_td=True: a PERDQN memory needs a capacity of at least 2 (got %d): the reference's "
+                                 "SumTree._propagate never ends for a tree of one leaf" % small[0])
+        self.learn_reference_td = bool(learn_reference_td)
         # learn_rollout=True: every PPO brain trains through rl_learn_ppo on rollouts drawn from the rows its current weights made
         # (PPO.py:71-77, 136-162).  A keyword of its own, like learn_prioritized.  Checked before a device is touched.
         self._opt_in("rollout", learn_rollout, learn, brains)
@@ -380,6 +397,7 @@ class Environment:
         self._learned = False       # ... learn_reference() ran since the last step()
         self.reference_calls = []   # ... every Call made so far as (n_epi, Call), while log_reference_calls is on (tests, diagnostics)
         self.reference_choices = []  # ... and per PERD3QN train() (n_epi, brain, indices, slots, bracket) as device tensors, likewise
+        #                              (per PERDQN train_model(): (n_epi, brain, idxs, slots, points), idxs the reference's TREE indices)
         if learn == "reference":    # every condition is checked before a device is touched
             self._check_reference(brains, n_worlds, static_families, training, learn_every, steps_given)
         self.best_agents = []
@@ -486,8 +504,10 @@ class Environment:
         learner (DeviceLearner(prioritized=True)) whose priorities, one per ring row, stay on the device."""
         from ..learn_reference import KINDS, PPO_LIST_MAX, BrainSpec, ReferenceSchedule
         slack = _lib.slot_cap_for(max_agents)
-        self.schedule = ReferenceSchedule([BrainSpec.of(b, prioritized=True) if self.learn_reference_prioritized else BrainSpec.of(b)
-                                           for b in brains], slack)
+        opt = dict(prioritized=True) if self.learn_reference_prioritized else {}
+        if self.learn_reference_td:   # (the keyword is only passed where it is given: every other run builds the specs it built)
+            opt["td"] = True
+        self.schedule = ReferenceSchedule([BrainSpec.of(b, **opt) for b in brains], slack)
         specs = self.schedule.specs
         self.ring_floor = slack
         self.ring_rows = [self.schedule.ring_rows(k) if specs[k] else slack for k in range(len(brains))]
@@ -504,11 +524,17 @@ class Environment:
                     setattr(narrow, name, getattr(wide, name))
             elif s.method == "PERD3QN":
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=ring, prioritized=True)
+            elif s.method == "PERDQN":   # rl_learn_td on the slots the tree walk names; the gate is the schedule's (train_start)
+                l = self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=ring, td_priority=True)
+                l.min_size = 0
             else:
                 self.learners[k] = DeviceLearner(brains[k], self.worlds.device, ring=ring)
         frozen = ["%d (%s)" % (k, b.method) for k, b in enumerate(brains) if k not in self.learners]
         if frozen:
-            warn_inference_only(frozen, KINDS, mode="reference_prioritized" if self.learn_reference_prioritized else "reference")
+            if self.learn_reference_td:   # (with it only PERD3QN brains without their own keyword can be left)
+                warn_inference_only(frozen, KINDS + (("PERD3QN",) if self.learn_reference_prioritized else ()) + ("PERDQN",), mode="reference_td")
+            else:
+                warn_inference_only(frozen, KINDS, mode="reference_prioritized" if self.learn_reference_prioritized else "reference")
         if not self.learners:
             raise ValueError("learn='reference': none of the brains is of a kind that trains in this mode (DQN, D3QN, PPO)")
 
@@ -533,8 +559,12 @@ class Environment:
                 self.worlds.launches += 1
             elif c.kind == "ppo":
                 self._learn_ppo(c.brain, c.slots, c.wide)
+            elif c.kind == "store" and l.spec.family == "td":   # PERDQN: Memory.add for the rows behind the tick's last train_model()
+                self.worlds.store_td_reference([l], [self.schedule.specs[c.brain].capacity], [c.store[0]], [c.store[1]])
             elif c.kind == "store":   # PERD3QN: store()'s priority for the rows behind the tick's last train()
                 self.worlds.store_prioritized_reference([l], [self.schedule.specs[c.brain].capacity], [c.store[0]], [c.store[1]])
+            elif c.uniforms is not None and l.spec.family == "td":
+                self._learn_td_reference(n_epi, c)
             elif c.uniforms is not None:
                 self._learn_prioritized_reference(n_epi, c)
             else:
@@ -562,6 +592,23 @@ class Environment:
         self.worlds.learn([l], 1, slots=slots)
         if self.log_reference_calls:
             self.reference_choices.append((n_epi, c.brain, indices[0], slots[0, 0], bracket[0]))
+
+    def _learn_td_reference(self, n_epi, c):
+        """One PERDQNAgent.train_model() of learn_reference_td=True: epsilon's decay on the host (PERDQN.py:132-133, a Python double, in
+        front of the draw), then Memory.add for the rows stored since the last group, the stratified walk on the call's uniforms,
+        rl_learn_td on the slots it leaves on the device, and the tree's update from the priorities that has written -- four launches,
+        nothing read back."""
+        l, capacity = self.learners[c.brain], self.schedule.specs[c.brain].capacity
+        if l.brain.epsilon > l.brain.epsilon_min:
+            l.brain.epsilon -= l.brain.epsilon_decay
+        self.worlds.store_td_reference([l], [capacity], [c.store[0]], [c.store[1]])
+        idxs, slots, points = self.worlds.sample_td_reference([l], [capacity], [c.store[0] + c.store[1]], [c.uniforms],   # (the rows stored as of THIS call)
+                                                              with_points=self.log_reference_calls)
+        l.sync_target = bool(c.sync_target)
+        self.worlds.learn([l], 1, slots=slots)
+        self.worlds.update_td_reference([l], [capacity], idxs, slots)
+        if self.log_reference_calls:
+            self.reference_choices.append((n_epi, c.brain, idxs[0], slots[0, 0], points[0]))
 
     def _opt_in(self, keyword, value, learn, brains):
         """learn_<keyword>=True, the environment's spelling of DeviceLearner(..., <keyword>=True): None or True, with learn='device' and
@@ -949,12 +996,16 @@ class Environment:
         if self.learn == "reference":
             frozen = [k for k in range(len(self.brains)) if k not in self.learners]
             prio = [k for k in sorted(self.learners) if self.learners[k].spec.family == "prioritized"]
+            td = [k for k in sorted(self.learners) if self.learners[k].spec.family == "td"]
             return ("brains %s trained on the device on the reference's own schedule and draws (learn='reference': per agent of the post-step "
                     "list, when its age is a multiple of train_freq or it died; minibatches by random.sample over the replay deque)"
                     % sorted(self.learners)
                     + ("; the minibatches of brains %s by np.random.choice's rule on np.random's uniforms, the priorities kept and the cdf "
                        "walked on the device (learn_reference_prioritized=True: rl_learn_prioritized_store_ref, rl_learn_prioritized_choice; a "
                        "uniform within about 2^-21 of a cdf boundary may name the neighbouring row)" % prio if prio else "")
+                    + ("; the minibatches of brains %s by Memory.sample's stratified walk on random.random()'s uniforms, the sum tree kept on the "
+                       "device in float64 with the reference's rounding order (learn_reference_td=True: rl_learn_td_tree_store, "
+                       "rl_learn_td_tree_sample, rl_learn_td_tree_update; a draw that the reference would repeat ends the run)" % td if td else "")
                     + ("; brains %s as loaded / initialised (their kinds do not learn in this mode)" % frozen if frozen else ""))
         frozen = [k for k in range(len(self.brains)) if k not in self.learners]
         by = {name: [k for k in sorted(self.learners) if self.learners[k].spec is ENTRY[name]] for name in self._NOTES}
@@ -1240,6 +1291,12 @@ def warn_inference_only(frozen=None, kinds=("DQN",), draw=None, mode="device"):
                       "memory's sum tree accumulates rounding in update order and append_sample makes forward passes per store: PERDQN brains do "
                       "not train in this mode yet; learn='device' trains them on its own schedule)."
                       % (", ".join(kinds), ", ".join(frozen)), stacklevel=4)
+        return
+    if frozen is not None and mode == "reference_td":
+        warnings.warn("learn='reference' with learn_reference_td=True trains the %s brains of this run; brains %s are of other kinds: they "
+                      "stay inference only -- brain.learn() is a no-op for them and their weights are NOT updated (PERD3QN brains train in this "
+                      "mode with learn_reference_prioritized=True; learn='device' trains them on its own schedule)."
+                      % (", ".join(kinds[:-1]) + " and " + kinds[-1], ", ".join(frozen)), stacklevel=4)
         return
     if frozen is not None and mode == "reference":
         warnings.warn("learn='reference' trains the %s brains of this run; brains %s are of other kinds: they stay inference only -- "

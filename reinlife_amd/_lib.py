@@ -83,6 +83,20 @@ class PrioChoice(C.Structure):  # rl_prio_choice
                 + [(n, C.c_void_p) for n in ("u", "indices", "slots", "bracket", "work")])
 
 
+class TdTreeStore(C.Structure):  # rl_td_tree_store
+    _fields_ = [("tree", C.c_void_p)] + [(n, C.c_longlong) for n in ("capacity", "ring_rows", "first_row", "n_rows")]
+
+
+class TdTreeSample(C.Structure):  # rl_td_tree_sample
+    _fields_ = ([("tree", C.c_void_p)] + [(n, C.c_longlong) for n in ("capacity", "ring_rows", "stored")] + [("n", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("u", "idxs", "slots", "s", "leaves")])
+
+
+class TdTreeUpdate(C.Structure):  # rl_td_tree_update
+    _fields_ = ([("tree", C.c_void_p)] + [(n, C.c_longlong) for n in ("capacity", "ring_rows")] + [("n", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("idxs", "slots")])
+
+
 class Ppo(C.Structure):  # rl_ppo
     _fields_ = [("lmbda", C.c_float), ("eps_clip", C.c_float), ("k_epoch", C.c_int32)] + [(n, C.c_void_p) for n in ("seen", "fresh", "keys")]
 
@@ -109,6 +123,9 @@ LEARN_PPO_WIDE_MAX = 2048   # RL_LEARN_PPO_WIDE_MAX: the rows of a rollout at mo
 LEARN_TD_WIDE_MAX = 2048   # RL_LEARN_TD_WIDE_MAX: the rows of a minibatch at most (rl_learn_td_wide)
 LEARN_CHOICE_MAX = 64   # RL_LEARN_CHOICE_MAX: the draws of one rl_learn_prioritized_choice call per learner at most
 ERR_NO_DISTRIBUTION = 7   # error-flag code: rl_learn_prioritized_choice found priorities np.random.choice would refuse
+LEARN_TD_TREE_BATCH_MAX = 64   # RL_LEARN_TD_TREE_BATCH_MAX: the draws / updates of one rl_learn_td_tree_sample / _update call per learner at most
+ERR_TREE_INDEX = 9   # error-flag code: rl_learn_td_tree_update was handed a leaf index outside the tree's leaves or a slot outside the ring
+ERR_TREE_REDRAW = 8   # error-flag code: rl_learn_td_tree_sample drew a leaf no row has reached (the reference would draw again), or found no total
 
 
 class Brain(C.Structure):
@@ -183,6 +200,9 @@ ABI = [
     ("rl_learn_td_draw_rank", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),
     ("rl_learn_td_stamp", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, _P]),
     ("rl_learn_td", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),
+    ("rl_learn_td_tree_store", C.c_int, [_P, C.POINTER(Learner), C.POINTER(TdPrio), C.POINTER(TdTreeStore), C.c_int, _P]),
+    ("rl_learn_td_tree_sample", C.c_int, [_P, C.POINTER(Learner), C.POINTER(TdPrio), C.POINTER(TdTreeSample), C.c_int, _P]),
+    ("rl_learn_td_tree_update", C.c_int, [_P, C.POINTER(Learner), C.POINTER(TdPrio), C.POINTER(TdTreeUpdate), C.c_int, _P]),
     ("rl_learn_td_wide_supported", C.c_int, [C.c_int]),
     ("rl_learn_td_wide_work_bytes", C.c_size_t, [C.c_int, C.c_int]),
     ("rl_learn_td_wide_draw", C.c_int, [_P, C.POINTER(Learner), C.POINTER(Replay), C.POINTER(TdPrio), C.c_int, C.c_int, _P, _P]),

@@ -15,7 +15,7 @@ TUNE = bool(os.environ.get("RL_TUNE"))
 TAG = "_prof" if PROFILE else "_tune" if TUNE else ("_" + os.environ["RL_LIB_TAG"] if os.environ.get("RL_LIB_TAG") else "")
 TUNE_LIB_PATH = os.path.join(LIB_DIR, "libreinlife_hip_tune.so")
 LIB_PATH = os.path.join(LIB_DIR, "libreinlife_hip%s.so" % TAG)
-SOURCES = ["rl_world.hip", "rl_run.hip", "rl_policy.hip", "rl_render.hip", "rl_learn.hip", "rl_learn_dueling.hip", "rl_learn_prio.hip", "rl_learn_ppo.hip", "rl_learn_td.hip", "rl_learn_merge.hip", "rl_learn_wide.hip", "rl_learn_dueling_wide.hip", "rl_learn_rank.hip", "rl_learn_ppo_wide.hip", "rl_learn_td_wide.hip", "rl_learn_prio_ref.hip", "rl_capi.hip"]
+SOURCES = ["rl_world.hip", "rl_run.hip", "rl_policy.hip", "rl_render.hip", "rl_learn.hip", "rl_learn_dueling.hip", "rl_learn_prio.hip", "rl_learn_ppo.hip", "rl_learn_td.hip", "rl_learn_merge.hip", "rl_learn_wide.hip", "rl_learn_dueling_wide.hip", "rl_learn_rank.hip", "rl_learn_ppo_wide.hip", "rl_learn_td_wide.hip", "rl_learn_prio_ref.hip", "rl_learn_td_ref.hip", "rl_capi.hip"]
 # (object suffix, extra flags) per source: rl_run.hip is compiled as TWO units side by side (RL_RUN_UNIT, see the file) -- one compiler for all
 # of k_run's instantiations is what a forced build waits for
 UNITS = {"rl_run.hip": [("", ["-DRL_RUN_UNIT=0"]), ("_all", ["-DRL_RUN_UNIT=1"])]}

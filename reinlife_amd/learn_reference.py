@@ -34,6 +34,16 @@ of PPO_LIST_MAX + slack rows and may not grow beyond PPO_LIST_MAX rows (ValueErr
        [first, first + count)), and a tick that stored rows ends with a Call of kind "store" for those not yet stamped: no group spans a
        train() and none exceeds the rows of one tick, that is `slack` rows.
 
+  PERDQN (PERDQN.py:130-133, 188-195, 280-298; only where the caller opts in, BrainSpec.of(brain, td=True))   store (append_sample: the
+       row enters the sum tree with the constant priority, no draw); on the trigger, if min(stored, memory_size) >= train_start, one
+       train_model() and then model -> target_model (sync_target on every such Call).  Memory.sample(batch_size) calls random.uniform once
+       per segment -- random.uniform(a, b) is a + (b - a) * random.random() -- as long as no draw lands on a leaf no row has reached: the
+       Call carries u = [random.random() for _ in range(batch_size)], drawn HERE from the process-global `random` stream where the
+       reference's calls fall, and the device keeps the tree and walks it (rl_learn_td_tree_sample): `slots` and `indices` are None.  The
+       rows stored since the last group enter the tree in front of every train_model() (`store`), and a tick ends with a Call of kind
+       "store" for the rest: PERD3QN's rules.  Below the gate the trigger's target copy changes nothing (the two are equal since the last
+       update): no call.
+
 Brains of other kinds are not scheduled: their rows are counted by nobody here and they make no draws."""
 import random
 from typing import NamedTuple
@@ -44,7 +54,7 @@ DQN_CAPACITY, DQN_BATCH, DQN_STEPS, DQN_GATE = 50_000, 32, 5, 1000   # DQN.py:15
 PPO_LIST_MAX = 2048      # the rows of the longest PPO list a call can train on (rl_learn_ppo_wide's batch limit)
 PPO_NARROW_MAX = 32      # up to here a list goes to rl_learn_ppo, beyond to rl_learn_ppo_wide
 KINDS = ("DQN", "D3QN", "PPO")   # the brain methods this schedule trains
-OPT_IN_KINDS = ("PERD3QN",)      # ... and those it trains where the caller asks for it (BrainSpec.of(brain, prioritized=True))
+OPT_IN_KINDS = ("PERD3QN", "PERDQN")   # ... and those it trains where the caller asks for it (BrainSpec.of(brain, prioritized=True) / td=True)
 
 
 class Call(NamedTuple):
@@ -54,7 +64,9 @@ class Call(NamedTuple):
     `indices` what random.sample drew, as deque indices [n_steps][batch] (PPO, sync: None).
     PERD3QN: kind "learn" carries `uniforms` [batch] float64 -- np.random.choice's doubles, for the device's cdf walk; slots and indices
     are None -- and `store` = (first row, rows): the group store() stamps in front of that train(); `size` is len(memory).  kind
-    "store": the stamp alone, of the rows a tick stored behind its last train()."""
+    "store": the stamp alone, of the rows a tick stored behind its last train().
+    PERDQN: the same two kinds; `uniforms` are random.random()'s doubles for Memory.sample's stratified walk, `store` the rows that enter
+    the sum tree in front of that train_model(), sync_target is always on."""
     kind: str
     brain: int
     slots: np.ndarray = None
@@ -73,11 +85,13 @@ class BrainSpec(NamedTuple):
     batch: int = DQN_BATCH
     exploration: int = 0
     soft_update_freq: int = 1
+    train_start: int = 0             # PERDQN: the rows the memory must hold before train_model() runs (PERDQN.py:192)
 
     @classmethod
-    def of(cls, brain, prioritized=False):
+    def of(cls, brain, prioritized=False, td=False):
         """The spec of a brain object by its own attributes, or None for a kind this schedule does not train.  prioritized=True: a
-        PERD3QN brain gets a spec too (Environment's learn_reference_prioritized=True)."""
+        PERD3QN brain gets a spec too (Environment's learn_reference_prioritized=True); td=True: a PERDQN brain does
+        (learn_reference_td=True)."""
         method, freq = getattr(brain, "method", None), int(getattr(brain, "train_freq", 20))
         if method == "DQN":
             return cls("DQN", freq)
@@ -87,6 +101,8 @@ class BrainSpec(NamedTuple):
             return cls("PPO", freq, PPO_LIST_MAX, 0)
         if method == "PERD3QN" and prioritized:
             return cls("PERD3QN", freq, int(brain.capacity), int(brain.batch_size), int(brain.exploration), int(brain.soft_update_freq))
+        if method == "PERDQN" and td:
+            return cls("PERDQN", freq, int(brain.memory_size), int(brain.batch_size), train_start=int(brain.train_start))
         return None
 
 
@@ -123,7 +139,7 @@ class ReferenceSchedule:
         self.stored = [0] * n        # rows stored so far, per brain
         self.listed = [0] * n        # PPO: the row the current list starts at
         self.stale = [False] * n     # D3QN, PERD3QN: an update was made since the last eval -> target copy
-        self.stamped = [0] * n       # PERD3QN: the rows whose priority store() has been queued for
+        self.stamped = [0] * n       # PERD3QN, PERDQN: the rows whose priority store() / Memory.add has been queued for
         self.calls = 0               # Calls handed out so far
 
     def ring_rows(self, brain):
@@ -152,8 +168,8 @@ class ReferenceSchedule:
             self.stored[b] += 1                                   # memorize() / put_data()
             trigger = age % s.train_freq == 0 or dead
             out += getattr(self, "_" + s.method.lower())(b, s, n_epi, trigger)
-        for b in sorted(per_brain):                               # PERD3QN: the rows stored behind the tick's last train()
-            if self.specs[b].method == "PERD3QN" and self.stamped[b] < self.stored[b]:
+        for b in sorted(per_brain):                               # PERD3QN, PERDQN: the rows stored behind the tick's last train()
+            if self.specs[b].method in OPT_IN_KINDS and self.stamped[b] < self.stored[b]:
                 out.append(Call("store", b, store=self._store_group(b)))
         self.calls += len(out)
         return out
@@ -201,6 +217,12 @@ class ReferenceSchedule:
             self.stale[b] = False
             return [Call("sync", b)]
         return []
+
+    def _perdqn(self, b, s, n_epi, trigger):
+        if not trigger or self.size(b) < s.train_start:           # PERDQN.py:191-192: below the gate the copy changes nothing
+            return []
+        u = np.array([random.random() for _ in range(s.batch)], np.float64)   # Memory.sample: one random.uniform per segment
+        return [Call("learn", b, None, True, self.size(b), None, False, u, self._store_group(b))]
 
     def _ppo(self, b, s, n_epi, trigger):
         n = self.size(b)

@@ -255,6 +255,13 @@ class DeviceWorlds:
         if e[0] != 0:
             hint = (" -- rl_learn_prioritized_choice: the priorities of learner [world] give no distribution (all zero, a NaN or a negative "
                     "one), where np.random.choice raises ValueError") if int(e[0]) == _lib.ERR_NO_DISTRIBUTION else ""
+            if int(e[0]) == _lib.ERR_TREE_REDRAW:
+                hint = (" -- rl_learn_td_tree_sample: a draw of learner [world] ended on a leaf of the sum tree no row has reached (or the "
+                        "tree's total is no positive finite number), where the reference's Memory.sample draws again: the run has left the "
+                        "reference's draw order")
+            if int(e[0]) == _lib.ERR_TREE_INDEX:
+                hint = (" -- rl_learn_td_tree_update: entry [detail 0] of learner [world]'s batch names a leaf index ([detail 1]) outside the "
+                        "tree's leaves, or a slot outside the ring: the entry was skipped")
             raise _lib.ReinLifeHipError("device error flag: code %d world %d detail (%d, %d)" % tuple(int(x) for x in e) + hint)
 
     def readback(self, tensors):
@@ -615,6 +622,74 @@ class DeviceWorlds:
         self._choice_keep = u_dev   # (the launch reads the uniforms asynchronously)
         self.launches += 1
         return indices, slots, bracket
+
+    def _reference_tree_args(self, who, learners, capacities):
+        """The common arguments of the three sum-tree calls; keeps learner.ref_tree, the reference's SumTree.tree as a zeroed device
+        float64 [2 C - 1], on the learners, made at a learner's first call; another capacity later is refused."""
+        n = len(learners)
+        if n < 1 or n > _lib.MAX_CAPTURE_BRAINS:
+            raise ValueError("%s(): 1 to %d learners per call (got %d)" % (who, _lib.MAX_CAPTURE_BRAINS, n))
+        if any(l.spec.side is not _lib.TdPrio for l in learners):
+            raise ValueError("%s(): every learner must be a PERDQN one (DeviceLearner(..., td_priority=True))" % who)
+        for l, c in zip(learners, capacities):
+            if not 2 <= int(c) <= 2 ** 30:
+                raise ValueError("%s(): capacity must be in [2, 2^30] (got %r): the reference's SumTree._propagate never ends for a tree of one leaf" % (who, c))
+            if getattr(l, "ref_tree", None) is None:   # (once per learner, at its first call: no later call allocates)
+                l.ref_tree = torch.zeros(2 * int(c) - 1, dtype=torch.float64, device=self.device)
+            elif l.ref_tree.numel() != 2 * int(c) - 1:
+                raise ValueError("%s(): this learner's tree was built for a capacity of %d, not %d: a memory keeps its capacity (a new tree "
+                                 "would lose its priorities)" % (who, (l.ref_tree.numel() + 1) // 2, int(c)))
+        return n, (_lib.Learner * n)(*[l.struct() for l in learners]), (_lib.TdPrio * n)(*[l.side_struct(_lib.TdPrio) for l in learners])
+
+    def store_td_reference(self, learners, capacities, first_rows, n_rows):
+        """Memory.add (PERDQN.py:276-278) as learn="reference" uses it (rl_learn_td_tree_store, one launch, queued on the current stream):
+        for learner i the rows [first_rows[i], first_rows[i] + n_rows[i]) -- numbered from 0 in storage order, row a at memory index
+        a % capacities[i] and in slot a % ring rows of learner.priority -- enter learner.ref_tree in row order with append_sample's
+        constant priority, learner.p_new.  n_rows[i] at most ring rows - capacities[i]."""
+        n, arr, sides = self._reference_tree_args("store_td_reference", learners, capacities)
+        groups = (_lib.TdTreeStore * n)(*[_lib.TdTreeStore(_ptr(l.ref_tree), int(c), int(l.ring["state"].shape[0]), int(a), int(m))
+                                          for l, c, a, m in zip(learners, capacities, first_rows, n_rows)])
+        _lib.check(self.lib.rl_learn_td_tree_store(self.handle, arr, sides, groups, n, self._stream()), "rl_learn_td_tree_store")
+        self.launches += 1
+
+    def sample_td_reference(self, learners, capacities, stored, uniforms, with_points=False):
+        """Memory.sample's stratified draw (PERDQN.py:280-298) from uniforms the host has drawn (rl_learn_td_tree_sample, one launch, queued
+        on the current stream): learner i's tree of capacities[i] leaves with stored[i] rows stored so far; uniforms[i] =
+        [random.random() for _ in range(batch)], all of one batch <= 64.  Returns device tensors: idxs int32 [n, batch] (the reference's
+        TREE indices), slots int32 [n, 1, batch] (what learn(learners, 1, slots=...) takes) and, with_points=True, each draw's s and the
+        leaf it found as float64 [n, batch, 2] (else None).  A draw that lands on a leaf no row has reached, where the reference draws
+        again, sets the error flag, code _lib.ERR_TREE_REDRAW."""
+        n, arr, sides = self._reference_tree_args("sample_td_reference", learners, capacities)
+        u = np.ascontiguousarray(np.asarray(uniforms, np.float64).reshape(n, -1))
+        batch = u.shape[1]
+        if not 1 <= batch <= _lib.LEARN_TD_TREE_BATCH_MAX:
+            raise ValueError("sample_td_reference(): 1 to %d uniforms per learner (got %d)" % (_lib.LEARN_TD_TREE_BATCH_MAX, batch))
+        u_dev = torch.as_tensor(u, device=self.device)
+        idxs = torch.zeros((n, batch), dtype=torch.int32, device=self.device)
+        slots = torch.zeros((n, 1, batch), dtype=torch.int32, device=self.device)
+        points = torch.zeros((2, n, batch), dtype=torch.float64, device=self.device) if with_points else None
+        draws = (_lib.TdTreeSample * n)(*[_lib.TdTreeSample(_ptr(l.ref_tree), int(c), int(l.ring["state"].shape[0]), int(s), batch, _ptr(u_dev[i]),
+                                                            _ptr(idxs[i]), _ptr(slots[i]), _ptr(points[0, i]) if with_points else None,
+                                                            _ptr(points[1, i]) if with_points else None)
+                                          for i, (l, c, s) in enumerate(zip(learners, capacities, stored))])
+        _lib.check(self.lib.rl_learn_td_tree_sample(self.handle, arr, sides, draws, n, self._stream()), "rl_learn_td_tree_sample")
+        self._choice_keep = u_dev   # (the launch reads the uniforms asynchronously)
+        self.launches += 1
+        return idxs, slots, points.permute(1, 2, 0) if with_points else None
+
+    def update_td_reference(self, learners, capacities, idxs, slots):
+        """train_model's priority loop (PERDQN.py:175-177) behind learn() (rl_learn_td_tree_update, one launch, queued on the current
+        stream): for learner i, in order, the leaf idxs[i][j] of learner.ref_tree gets the priority rl_learn_td has just written to
+        learner.priority[slots[i][j]].  idxs and slots: the device tensors sample_td_reference() returned."""
+        n, arr, sides = self._reference_tree_args("update_td_reference", learners, capacities)
+        idxs, slots = idxs.reshape(n, -1), slots.reshape(n, -1)
+        if idxs.dtype != torch.int32 or slots.dtype != torch.int32 or idxs.shape != slots.shape or not idxs.is_contiguous() or not slots.is_contiguous():
+            raise ValueError("update_td_reference(): idxs and slots must be contiguous int32 device tensors of one shape")
+        batches = (_lib.TdTreeUpdate * n)(*[_lib.TdTreeUpdate(_ptr(l.ref_tree), int(c), int(l.ring["state"].shape[0]), int(idxs.shape[1]),
+                                                              _ptr(idxs[i]), _ptr(slots[i])) for i, (l, c) in enumerate(zip(learners, capacities))])
+        _lib.check(self.lib.rl_learn_td_tree_update(self.handle, arr, sides, batches, n, self._stream()), "rl_learn_td_tree_update")
+        self._tree_keep = (idxs, slots)   # (the launch reads them asynchronously)
+        self.launches += 1
 
     def _draw_side_rank(self, who, draw, learners, n_steps, stratified, side, one_of):
         """draw_prioritized_rank / draw_td_rank: the C entry `draw`, fed the learners' side structs and their order / cum / work buffers.
